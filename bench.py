@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- reads -> unitigs throughput on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg 3|4|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg 3|4|5] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps, writes the last step's unitig set with --dump-outputs DIR (dump_outputs)
+and prints the result line (metric, value, ms_per_step, counts, stage_ms).  --full adds what the headline does not
+need: the output checks and device-side verification (checks, digest, verify; exit 3 when one fails), roofline,
+cpu_baseline and the end-to-end CLI leg (e2e, t_e2e_s).
 
 A "step" is one full pass of the hot path (count -> compact -> glue) over one resident
 batch of synthetic reads.  Workload at N=1: BASELINE config 3 (100 M x 150 bp synthetic
@@ -59,16 +64,22 @@ def pmc_traffic(kernel_key, cfg):
     (bench_micro/pmc_bench.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs; bytes = (f * FETCH_SIZE + WRITE_SIZE) * 1024 with
     the per-access-pattern factor f calibrated in profiles/r03_counter_calibration.csv: 2 for wide coalesced reads -- the
     gfx950 FETCH_SIZE halving of MI355X_MICROARCH.md section HBM -- 1 for kernels whose reads are random gathers).
+    A stage (several keys) is all launches of its kernels in ONE step: the table's launches over the steps it profiled, which its
+    header states as profiled_steps=N (tables without it were taken over 2 steps).
     -> (bytes or None, first line of the CSV: the commit it was taken at)"""
+    import re
     keys = kernel_key if isinstance(kernel_key, (list, tuple)) else [kernel_key]
-    tot, found, stamp = 0.0, False, None
+    tot, found, stamp, steps = 0.0, False, None, 2
     try:
         for line in open(pmc_csv(cfg)):
             if line.startswith("#"):
-                stamp = line[1:].strip(); continue
+                stamp = line[1:].strip()
+                m = re.search(r"profiled_steps=(\d+)", stamp)
+                steps = int(m.group(1)) if m else 2
+                continue
             row = line.rstrip("\n").rsplit(",", 5)          # kernel names contain commas
             if len(row) == 6 and row[1].isdigit() and any(x in row[0] for x in keys):
-                tot += float(row[5]) * float(row[1]) / 2 * 1e9 if len(keys) > 1 else float(row[5]) * 1e9   # (a stage: all launches of its kernels in one of the 2 profiled steps)
+                tot += float(row[5]) * float(row[1]) / steps * 1e9 if len(keys) > 1 else float(row[5]) * 1e9
                 found = True
                 if len(keys) == 1:
                     break
@@ -285,6 +296,237 @@ def cli_end_to_end(lib, k, amin, read_len, gen_cfg, n_reads, device_id):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+M64 = (1 << 64) - 1
+
+
+def _packed_bases(a64, start, m):
+    """bases [start, start + m) (m <= 32) of the 2-bit unitig arena seen as little-endian uint64 words: base i in bits 2i"""
+    import numpy as np
+    bit = start.astype(np.uint64) * np.uint64(2)
+    w = (bit >> np.uint64(6)).astype(np.int64)
+    s = bit & np.uint64(63)
+    x = (a64[w] >> s) | np.where(s > 0, a64[w + 1] << ((np.uint64(64) - s) & np.uint64(63)), np.uint64(0))
+    return x & np.uint64(M64 >> (64 - 2 * m))
+
+
+def _revcomp_bases(x, m):
+    """reverse complement of m bases packed as by _packed_bases"""
+    import numpy as np
+    x = ~x
+    for sh, mask in ((2, 0x3333333333333333), (4, 0x0F0F0F0F0F0F0F0F), (8, 0x00FF00FF00FF00FF), (16, 0x0000FFFF0000FFFF), (32, 0x00000000FFFFFFFF)):
+        sh, mask = np.uint64(sh), np.uint64(mask)
+        x = ((x >> sh) & mask) | ((x & mask) << sh)
+    return x >> np.uint64(2 * (32 - m))
+
+
+def _mix64(x):
+    import numpy as np
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def dump_outputs(g, out_dir, k, rank=0, world=1):
+    """--dump-outputs: the unitig set + KC the last timed step left in HBM, as float .npy files that do not depend on the library's
+    unitig order or orientation (two builds compare file for file):
+      summary.npy        n_unitigs, unitig_bases, kc_sum, solid_count_sum, kmers_in_unitigs, set_digest (high, low 32 bits),
+                         cyclic unitigs, sampled unitigs, sample rate exponent
+      length_hist.npy    unitigs per length k .. k + 4094, the last bin counting every longer one
+      sample_len.npy, sample_kc.npy, sample_bases.npy
+                         a fixed sample of the linear unitigs (1 in 2^8 or fewer, chosen by a hash of their two end words, at most
+                         60 MB / world of these three files per rank), sorted by those words, length, KC and sequence: length, KC
+                         and the sequence in its canonical orientation, codes A0 C1 G2 T3, concatenated
+    With world > 1 every rank writes its own share as <name>_rank<r>.npy; all files of all ranks stay under 64 MB."""
+    import ctypes as C
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lib = g.lib
+    n, tb = C.c_uint64(), C.c_uint64()
+    g._ck(lib.cdbg_num_unitigs(g._h, C.byref(n), C.byref(tb)))
+    n, tb = n.value, tb.value
+    nb = (tb + 3) // 4
+    a64 = np.zeros(nb // 8 + 2, np.uint64)                    # (+ one word: _packed_bases reads the word after the last base's)
+    off = np.zeros(max(n, 1), np.uint64); ln = np.zeros(max(n, 1), np.uint32); kc = np.zeros(max(n, 1), np.uint64)
+    g._ck(lib.cdbg_fetch_unitigs_packed(g._h, a64.ctypes.data_as(C.POINTER(C.c_uint8)), nb, off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        ln.ctypes.data_as(C.POINTER(C.c_uint32)), kc.ctypes.data_as(C.POINTER(C.c_uint64))))
+    off, ln, kc = off[:n], ln[:n].astype(np.uint64), kc[:n]
+    dg = g.digest()
+    m = min(k, 32)
+    head = _packed_bases(a64, off, m)                          # first m bases, and the first m of the reverse complement
+    tail = _revcomp_bases(_packed_bases(a64, off + ln - np.uint64(m), m), m)
+    flip = head > tail
+    lo, hi = np.minimum(head, tail), np.maximum(head, tail)
+    # cyclic unitigs (first k - 1 bases == last k - 1 bases, as the oracle's canonical_unitig) start anywhere on their cycle: not sampled
+    p = min(k - 1, 32)
+    ov = off + ln - np.uint64(k - 1)
+    cyc = ((_packed_bases(a64, off, p) == _packed_bases(a64, ov, p))
+           & (_packed_bases(a64, off + np.uint64(k - 1 - p), p) == _packed_bases(a64, off + ln - np.uint64(p), p)))
+    h = _mix64(lo ^ _mix64(hi))
+    bits = 8
+    budget = (60 << 20) // world                              # bytes of sample_* per rank: 4 per base, 8 + 8 per unitig
+    while True:
+        pick = np.nonzero((h >> np.uint64(64 - bits) == 0) & ~cyc)[0]
+        if int(ln[pick].sum()) * 4 + 16 * len(pick) <= budget or bits == 64:
+            break
+        bits += 1
+    pick = pick[np.lexsort((kc[pick], ln[pick], hi[pick], lo[pick]))]
+    L = ln[pick].astype(np.int64)
+    seg = np.repeat(np.arange(len(pick)), L)
+    pos = np.arange(int(L.sum())) - np.repeat(np.cumsum(L) - L, L)
+    fl = flip[pick][seg]
+    j = off[pick].astype(np.int64)[seg] + np.where(fl, L[seg] - 1 - pos, pos)
+    code = (a64[j >> 5] >> ((j & 31) * 2).astype(np.uint64)) & np.uint64(3)
+    code = np.where(fl, np.uint64(3) - code, code).astype(np.float32)
+    # a unitig whose two end words are equal (one palindromic k-mer at an even k; for k > 32 also a longer one) has no orientation
+    # from them: the smaller of its two strands
+    starts = np.cumsum(L) - L
+    for i in np.nonzero(head[pick] == tail[pick])[0]:
+        s = code[starts[i]:starts[i] + L[i]]
+        r = (3 - s)[::-1]
+        if tuple(r) < tuple(s):
+            code[starts[i]:starts[i] + L[i]] = r
+    # unitigs equal in end words, length and KC (k > 32 only: two unitigs may share both end words): ordered by their sequences
+    lo_p, hi_p, ln_p, kc_p = lo[pick], hi[pick], ln[pick], kc[pick]
+    eq = np.zeros(len(pick), bool)
+    eq[1:] = (lo_p[1:] == lo_p[:-1]) & (hi_p[1:] == hi_p[:-1]) & (ln_p[1:] == ln_p[:-1]) & (kc_p[1:] == kc_p[:-1])
+    if eq.any():
+        order = np.arange(len(pick))
+        run = list(np.nonzero(~eq)[0]) + [len(pick)]
+        for b, e in zip(run[:-1], run[1:]):
+            if e - b > 1:
+                order[b:e] = sorted(range(b, e), key=lambda i: tuple(code[starts[i]:starts[i] + L[i]]))
+        code = np.concatenate([code[starts[i]:starts[i] + L[i]] for i in order])
+        pick = pick[order]
+    summary = [n, tb, dg["kc_sum"], dg["solid_count_sum"], dg["kmers_in_unitigs"], dg["set_digest"] >> 32, dg["set_digest"] & 0xFFFFFFFF,
+               int(cyc.sum()), len(pick), bits]
+    files = {"summary": np.array(summary, np.float64),
+             "length_hist": np.bincount(np.minimum(ln - np.uint64(k), np.uint64(4095)).astype(np.int64), minlength=4096).astype(np.float64),
+             "sample_len": ln[pick].astype(np.float64), "sample_kc": kc[pick].astype(np.float64), "sample_bases": code}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), arr)
+
+
+def check_outputs(a, g, st, step, sharded, dist, world, torch):
+    """--full: the bench checks its own output (outside the timed region), at full size -> (checks, digest, verify)"""
+    dig_last = g.digest()
+    checks = {}
+    if not sharded:
+        g.reset(); step()
+        checks["set_digest_equal_across_two_steps"] = g.digest()["set_digest"] == dig_last["set_digest"]
+    tot = {"n_occurrences": st["n_occurrences"], "n_solid": st["n_solid"], "n_unitigs": st["n_unitigs"], "unitig_bases": st["unitig_bases"],
+           "kc_sum": dig_last["kc_sum"], "solid_count_sum": dig_last["solid_count_sum"], "kmers_in_unitigs": dig_last["kmers_in_unitigs"],
+           "set_digest": dig_last["set_digest"]}
+    if sharded and dist is not None:
+        # every rank holds the unitigs it owns: sums (and the additive set digest) over the ranks describe the whole graph
+        keys = sorted(tot)
+        v = torch.tensor([(tot[x] + (1 << 63)) % (1 << 64) - (1 << 63) for x in keys], device="cuda", dtype=torch.int64)   # two's complement: wraps like uint64
+        dist.all_reduce(v, op=dist.ReduceOp.SUM)
+        tot = {x: int(v[i].item()) % (1 << 64) for i, x in enumerate(keys)}
+    exp_occ = a.reads * (a.read_len - a.k + 1)                   # synthetic reads carry no N: every position is a k-mer
+    if sharded or world == 1:
+        checks["n_occurrences == R*(L-k+1)"] = tot["n_occurrences"] == exp_occ
+    checks["sum(LN-k+1) == n_solid"] = tot["kmers_in_unitigs"] == tot["n_solid"]
+    checks["sum(KC) == sum(solid counts)"] = tot["kc_sum"] == tot["solid_count_sum"]
+    checks["unitig_bases == n_solid + U*(k-1)"] = tot["unitig_bases"] == tot["kmers_in_unitigs"] + tot["n_unitigs"] * (a.k - 1)
+    dig_last = dict(dig_last, set_digest=tot["set_digest"], kc_sum=tot["kc_sum"], kmers_in_unitigs=tot["kmers_in_unitigs"])
+
+    # ---- the unitig DEFINITION at full size, without the oracle (cdbg_verify, bcalm_amd/csrc/k_verify.h): the canonical k-mers
+    # spelled by the unitigs are exactly the solid set, each once (position count + two commutative 64-bit sums); no two unitig
+    # ends are each other's only link (maximality; single graph per rank only: a rank of a sharded job holds no link table) ----
+    vr = g.verify()
+    vu, vs = list(vr["unitig_kmers"]), list(vr["solid_kmers"])
+    if sharded and dist is not None:
+        v = torch.tensor([(x + (1 << 63)) % (1 << 64) - (1 << 63) for x in vu + vs], device="cuda", dtype=torch.int64)
+        dist.all_reduce(v, op=dist.ReduceOp.SUM)
+        allv = [int(x.item()) % (1 << 64) for x in v]
+        vu, vs = allv[:3], allv[3:]
+    checks["k-mers spelled by the unitigs == solid set (count, 2 x 64-bit commutative sums)"] = vu == vs and vu[0] == tot["n_solid"]
+    if vr["mergeable_ends"] is not None:
+        checks["no two unitig ends are each other's only link (every unitig maximal)"] = vr["mergeable_ends"] == 0
+    # edge conservation (cdbg_verify_edges; bidirected-graphs-in-bcalm2.md:85): the edges of the solid k-mer graph, counted from the
+    # count stage's keys in one global (k-1)-mer table, are exactly the inner adjacencies of the unitigs plus the links between
+    # their ends -- a unitig that runs THROUGH a branching junction (over-compaction) leaves a strictly positive shortfall
+    ve = vr["edges"]
+    if ve is not None:
+        checks["edges of the solid graph == links + 2 x inner adjacencies (every inner junction 1-in / 1-out)"] = ve["graph"] == ve["links"] + ve["inner"]
+    verify_info = {"unitig_kmers": [vu[0], "%016x" % vu[1], "%016x" % vu[2]], "solid_kmers": [vs[0], "%016x" % vs[1], "%016x" % vs[2]],
+                   "mergeable_ends": vr["mergeable_ends"], "closed_chains_cut": vr["closed_chains"], "edges": ve}
+    if vr.get("edges_error"):                              # (the edge pass could not run -- table too large for the card: said, not hidden)
+        verify_info["edges_error"] = vr["edges_error"]
+    return checks, dig_last, verify_info
+
+
+def roofline(a, st, acc):
+    """--full: every stage kernel against the HBM roofline, from the stage times of the timed steps"""
+    per_kernel, alg_total = alg_bytes(a.k, st, a.reads, a.read_len)
+    ms = {"k_scan<hist>": acc["ms_scan_hist"], "k_scan<emit>": acc["ms_scan_emit"], "k_count_fast": acc["ms_count"],
+          "k_compact_wave": acc["ms_compact"], GLUE_LABEL: acc["ms_glue"]}
+    # Deferred record placement (count_slices > 1; DESIGN.md section 3): part of the records is scattered by k_place on a second HIP stream WHILE
+    # k_count_fast counts the slice before, so "the scan" and "the count" are no longer two kernels one after the other.  They are rated as ONE entry:
+    # the algorithmic bytes of both (A1 + A2 + A3/2) over the WALL of the pair -- the scan kernel plus the count stage, which contains every wait for
+    # the placement; the placement stream's busy span is listed beside it and is not a summand.
+    PAIR = "k_scan<emit> + (k_place || k_count_fast)"
+    deferred = st.get("count_slices", 1) > 1
+    if deferred:
+        per_kernel[PAIR] = per_kernel["k_scan<emit>"] + per_kernel["k_count_fast"]
+        ms = {"k_scan<hist>": ms["k_scan<hist>"], PAIR: ms["k_scan<emit>"] + ms["k_count_fast"], "k_compact_wave": ms["k_compact_wave"], GLUE_LABEL: ms[GLUE_LABEL]}
+    gpu_ms = acc["ms_total"] / a.steps
+    Wk = W_OF(a.k)
+    pmc_keys = {"k_count_fast": "k_count_fast<%d, %d, " % (Wk, {1: 4096}.get(Wk, 2048)), "k_compact_wave": "k_compact_wave<",
+                "k_scan<emit>": "k_scan_fast<%d, 2" % Wk if a.k <= 127 else "k_scan<%d, 2" % Wk,
+                "k_scan<hist>": "k_scan_fast<%d, 0" % Wk if a.k <= 127 else "k_scan<%d, 0" % Wk,
+                GLUE_LABEL: ["k_join_bucket", "k_walk_", "k_rank8", "k_unitig_heads", "k_emit"]}   # (k_rank8 / k_unitig_heads / k_emit: only when the walk handed over to the ranking)
+    # every stage kernel with its own roofline numbers; the PMC table is quoted only while it was taken from THESE kernels
+    # (its header carries the content hash of the sources libcdbg.so was built from)
+    cur_hash = lib_srchash()
+    kernels = []
+    stamp = None
+    for name, tot_ms in ms.items():
+        if tot_ms <= 0:
+            continue
+        t_ms = tot_ms / a.steps
+        if name == "k_scan<hist>" and tot_ms < 0.25 * ms.get("k_scan<emit>", ms.get(PAIR, 0.0)):
+            # single-pass record layout: the histogram launch scans a 1/64 SAMPLE of the tiles to size the partition regions -- not a pass over A1
+            kernels.append({"kernel": name, "avg_launch_ms": t_ms, "note": "sampled histogram (1 tile in 64) that sizes the partition regions; not a full pass: no roofline figure"})
+            continue
+        ach = per_kernel[name] / (t_ms * 1e-3) / 1e9
+        if name == PAIR:
+            # (all launches of the three kernels in one step: the table's per-launch averages x launches / the profiled steps)
+            traffic, stamp_k = pmc_traffic([pmc_keys["k_scan<emit>"], "k_place<", pmc_keys["k_count_fast"]], a.cfg)
+            fresh = bool(stamp_k and cur_hash and ("srchash=%s" % cur_hash) in stamp_k) and not a.skewed and traffic is not None
+            stamp = stamp or stamp_k
+            kernels.append({"kernel": name, "alg_bytes_per_launch": per_kernel[name], "avg_launch_ms": t_ms, "achieved": ach, "frac": ach / HBM_PEAK_GBS,
+                            "traffic": traffic if fresh else None,
+                            "parts_ms": {"k_scan<emit> (alone on the chip)": acc["ms_scan_emit"] / a.steps,
+                                         "count stage, wall (k_count_fast once per slice; waits for the placement inside)": acc["ms_count"] / a.steps,
+                                         "k_place, busy span of the second stream (overlapped with the count stage: not a summand)": acc["ms_place"] / a.steps},
+                            "slices": st["count_slices"], "deferred_records": st["n_deferred_records"]})
+            continue
+        traffic, stamp_k = pmc_traffic(pmc_keys[name], a.cfg)
+        stamp = stamp or stamp_k
+        fresh = bool(stamp_k and cur_hash and ("srchash=%s" % cur_hash) in stamp_k) and not a.skewed
+        kernels.append({"kernel": name, "alg_bytes_per_launch": per_kernel[name], "avg_launch_ms": t_ms, "achieved": ach,
+                        "frac": ach / HBM_PEAK_GBS, "traffic": traffic if fresh else None})
+    # headline: of the kernels within 5 % of the longest one (scan and count are 0.2 ms apart at config 3 and swap places from
+    # run to run) the one FURTHEST from its roofline
+    rated = [x for x in kernels if "frac" in x]
+    longest = max(x["avg_launch_ms"] for x in rated)
+    head = min((x for x in rated if x["avg_launch_ms"] >= 0.95 * longest), key=lambda x: x["frac"])
+    fresh_any = any(x["traffic"] is not None for x in rated)
+    traffic_src = ("profiles/%s (separate rocprofv3 --pmc passes of this bench at this source hash; %s)" % (os.path.basename(pmc_csv(a.cfg)), stamp)
+                   if fresh_any else "none quoted: profiles/%s was taken from other kernel sources (%s; loaded library: srchash=%s) -- re-run bench_micro/pmc_bench.sh"
+                   % (os.path.basename(pmc_csv(a.cfg)), stamp or "absent", cur_hash))
+    return {"bound": "hbm", "kernel": head["kernel"], "achieved": head["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": head["frac"],
+            "traffic": head["traffic"], "traffic_source": traffic_src,
+            "alg_bytes_per_launch": head["alg_bytes_per_launch"], "avg_launch_ms": head["avg_launch_ms"],
+            "headline_rule": "of the stage kernels within 5 % of the longest: the lowest fraction",
+            "kernels": kernels,
+            "pipeline": {"alg_bytes": alg_total, "gpu_ms": gpu_ms,
+                         "achieved": alg_total / (gpu_ms * 1e-3) / 1e9,
+                         "frac": alg_total / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -297,6 +539,12 @@ def main():
     ap.add_argument("--read-len", type=int, default=None)
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--abundance-min", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the output checks and the device-side verification of the result, "
+                         "the roofline figures, the CPU baseline and the end-to-end CLI leg (without it: set-up, warm-up, the timed steps, "
+                         "--dump-outputs, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the unitig set of the last one as DIR/<name>.npy (float32/float64; see dump_outputs)")
     ap.add_argument("--cpu-sample-reads", type=int, default=None, help="reads of the CPU baseline's sample (default: 10 M for k <= 31, 6 M for k <= 63 -- the multithreaded restatement; 400 K per process of the scalar port beyond)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end leg (the bcalm CLI on a FASTA dump: t_e2e_s)")
@@ -415,52 +663,11 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     n_distinct = st["n_distinct"]
-    # ---- the bench checks its own output (outside the timed region): size-independent invariants at full size ----
-    dig_last = g.digest()
-    checks = {}
-    if not sharded:
-        g.reset(); step()
-        checks["set_digest_equal_across_two_steps"] = g.digest()["set_digest"] == dig_last["set_digest"]
-    tot = {"n_occurrences": st["n_occurrences"], "n_solid": st["n_solid"], "n_unitigs": st["n_unitigs"], "unitig_bases": st["unitig_bases"],
-           "kc_sum": dig_last["kc_sum"], "solid_count_sum": dig_last["solid_count_sum"], "kmers_in_unitigs": dig_last["kmers_in_unitigs"],
-           "set_digest": dig_last["set_digest"]}
-    if sharded and dist is not None:
-        # every rank holds the unitigs it owns: sums (and the additive set digest) over the ranks describe the whole graph
-        keys = sorted(tot)
-        v = torch.tensor([(tot[x] + (1 << 63)) % (1 << 64) - (1 << 63) for x in keys], device="cuda", dtype=torch.int64)   # two's complement: wraps like uint64
-        dist.all_reduce(v, op=dist.ReduceOp.SUM)
-        tot = {x: int(v[i].item()) % (1 << 64) for i, x in enumerate(keys)}
-    exp_occ = a.reads * (a.read_len - a.k + 1)                   # synthetic reads carry no N: every position is a k-mer
-    if sharded or world == 1:
-        checks["n_occurrences == R*(L-k+1)"] = tot["n_occurrences"] == exp_occ
-    checks["sum(LN-k+1) == n_solid"] = tot["kmers_in_unitigs"] == tot["n_solid"]
-    checks["sum(KC) == sum(solid counts)"] = tot["kc_sum"] == tot["solid_count_sum"]
-    checks["unitig_bases == n_solid + U*(k-1)"] = tot["unitig_bases"] == tot["kmers_in_unitigs"] + tot["n_unitigs"] * (a.k - 1)
-    dig_last = dict(dig_last, set_digest=tot["set_digest"], kc_sum=tot["kc_sum"], kmers_in_unitigs=tot["kmers_in_unitigs"])
-
-    # ---- the unitig DEFINITION at full size, without the oracle (cdbg_verify, bcalm_amd/csrc/k_verify.h): the canonical k-mers
-    # spelled by the unitigs are exactly the solid set, each once (position count + two commutative 64-bit sums); no two unitig
-    # ends are each other's only link (maximality; single graph per rank only: a rank of a sharded job holds no link table) ----
-    vr = g.verify()
-    vu, vs = list(vr["unitig_kmers"]), list(vr["solid_kmers"])
-    if sharded and dist is not None:
-        v = torch.tensor([(x + (1 << 63)) % (1 << 64) - (1 << 63) for x in vu + vs], device="cuda", dtype=torch.int64)
-        dist.all_reduce(v, op=dist.ReduceOp.SUM)
-        allv = [int(x.item()) % (1 << 64) for x in v]
-        vu, vs = allv[:3], allv[3:]
-    checks["k-mers spelled by the unitigs == solid set (count, 2 x 64-bit commutative sums)"] = vu == vs and vu[0] == tot["n_solid"]
-    if vr["mergeable_ends"] is not None:
-        checks["no two unitig ends are each other's only link (every unitig maximal)"] = vr["mergeable_ends"] == 0
-    # edge conservation (cdbg_verify_edges; bidirected-graphs-in-bcalm2.md:85): the edges of the solid k-mer graph, counted from the
-    # count stage's keys in one global (k-1)-mer table, are exactly the inner adjacencies of the unitigs plus the links between
-    # their ends -- a unitig that runs THROUGH a branching junction (over-compaction) leaves a strictly positive shortfall
-    ve = vr["edges"]
-    if ve is not None:
-        checks["edges of the solid graph == links + 2 x inner adjacencies (every inner junction 1-in / 1-out)"] = ve["graph"] == ve["links"] + ve["inner"]
-    verify_info = {"unitig_kmers": [vu[0], "%016x" % vu[1], "%016x" % vu[2]], "solid_kmers": [vs[0], "%016x" % vs[1], "%016x" % vs[2]],
-                   "mergeable_ends": vr["mergeable_ends"], "closed_chains_cut": vr["closed_chains"], "edges": ve}
-    if vr.get("edges_error"):                              # (the edge pass could not run -- table too large for the card: said, not hidden)
-        verify_info["edges_error"] = vr["edges_error"]
+    if a.dump_outputs:                                      # (before the checks of --full run the path once more)
+        dump_outputs(g, a.dump_outputs, a.k, rank, world)
+    checks, dig_last, verify_info = {}, None, None
+    if a.full:
+        checks, dig_last, verify_info = check_outputs(a, g, st, step, sharded, dist, world, torch)
 
     if dist is not None:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
@@ -473,64 +680,6 @@ def main():
         total_distinct = n_distinct
 
     if rank == 0:
-        per_kernel, alg_total = alg_bytes(a.k, st, a.reads, a.read_len)
-        ms = {"k_scan<hist>": acc["ms_scan_hist"], "k_scan<emit>": acc["ms_scan_emit"], "k_count_fast": acc["ms_count"],
-              "k_compact_wave": acc["ms_compact"], GLUE_LABEL: acc["ms_glue"]}
-        # Deferred record placement (count_slices > 1): part of the records is scattered by k_place on a second HIP stream WHILE
-        # k_count_fast counts the slice before, so "the scan" and "the count" are no longer two kernels one after the other.  They are rated as ONE entry:
-        # the algorithmic bytes of both (A1 + A2 + A3/2) over the WALL of the pair -- the scan kernel plus the count stage, which contains every wait for
-        # the placement; the placement stream's busy span is listed beside it and is not a summand.
-        PAIR = "k_scan<emit> + (k_place || k_count_fast)"
-        deferred = st.get("count_slices", 1) > 1
-        if deferred:
-            per_kernel[PAIR] = per_kernel["k_scan<emit>"] + per_kernel["k_count_fast"]
-            ms = {"k_scan<hist>": ms["k_scan<hist>"], PAIR: ms["k_scan<emit>"] + ms["k_count_fast"], "k_compact_wave": ms["k_compact_wave"], GLUE_LABEL: ms[GLUE_LABEL]}
-        gpu_ms = acc["ms_total"] / a.steps
-        Wk = W_OF(a.k)
-        pmc_keys = {"k_count_fast": "k_count_fast<%d, %d, " % (Wk, {1: 4096}.get(Wk, 2048)), "k_compact_wave": "k_compact_wave<",
-                    "k_scan<emit>": "k_scan_fast<%d, 2" % Wk if a.k <= 127 else "k_scan<%d, 2" % Wk,
-                    "k_scan<hist>": "k_scan_fast<%d, 0" % Wk if a.k <= 127 else "k_scan<%d, 0" % Wk,
-                    GLUE_LABEL: ["k_join_bucket", "k_walk_", "k_rank8", "k_unitig_heads", "k_emit"]}   # (k_rank8 / k_unitig_heads / k_emit: only when the walk handed over to the ranking)
-        # every stage kernel with its own roofline numbers; the PMC table is quoted only while it was taken from THESE kernels
-        # (its header carries the content hash of the sources libcdbg.so was built from)
-        cur_hash = lib_srchash()
-        kernels = []
-        stamp = None
-        for name, tot_ms in ms.items():
-            if tot_ms <= 0:
-                continue
-            t_ms = tot_ms / a.steps
-            if name == "k_scan<hist>" and tot_ms < 0.25 * ms.get("k_scan<emit>", ms.get(PAIR, 0.0)):
-                # single-pass record layout: the histogram launch scans a 1/64 SAMPLE of the tiles to size the partition regions -- not a pass over A1
-                kernels.append({"kernel": name, "avg_launch_ms": t_ms, "note": "sampled histogram (1 tile in 64) that sizes the partition regions; not a full pass: no roofline figure"})
-                continue
-            ach = per_kernel[name] / (t_ms * 1e-3) / 1e9
-            if name == PAIR:
-                # (all launches of the three kernels in one step: the table's per-launch averages x launches / the 2 profiled steps)
-                traffic, stamp_k = pmc_traffic([pmc_keys["k_scan<emit>"], "k_place<", pmc_keys["k_count_fast"]], a.cfg)
-                fresh = bool(stamp_k and cur_hash and ("srchash=%s" % cur_hash) in stamp_k) and not a.skewed and traffic is not None
-                stamp = stamp or stamp_k
-                kernels.append({"kernel": name, "alg_bytes_per_launch": per_kernel[name], "avg_launch_ms": t_ms, "achieved": ach, "frac": ach / HBM_PEAK_GBS,
-                                "traffic": traffic if fresh else None,
-                                "parts_ms": {"k_scan<emit> (alone on the chip)": acc["ms_scan_emit"] / a.steps,
-                                             "count stage, wall (k_count_fast once per slice; waits for the placement inside)": acc["ms_count"] / a.steps,
-                                             "k_place, busy span of the second stream (overlapped with the count stage: not a summand)": acc["ms_place"] / a.steps},
-                                "slices": st["count_slices"], "deferred_records": st["n_deferred_records"]})
-                continue
-            traffic, stamp_k = pmc_traffic(pmc_keys[name], a.cfg)
-            stamp = stamp or stamp_k
-            fresh = bool(stamp_k and cur_hash and ("srchash=%s" % cur_hash) in stamp_k) and not a.skewed
-            kernels.append({"kernel": name, "alg_bytes_per_launch": per_kernel[name], "avg_launch_ms": t_ms, "achieved": ach,
-                            "frac": ach / HBM_PEAK_GBS, "traffic": traffic if fresh else None})
-        # headline: of the kernels within 5 % of the longest one (scan and count are 0.2 ms apart at config 3 and swap places from
-        # run to run) the one FURTHEST from its roofline
-        rated = [x for x in kernels if "frac" in x]
-        longest = max(x["avg_launch_ms"] for x in rated)
-        head = min((x for x in rated if x["avg_launch_ms"] >= 0.95 * longest), key=lambda x: x["frac"])
-        fresh_any = any(x["traffic"] is not None for x in rated)
-        traffic_src = ("profiles/%s (separate rocprofv3 --pmc passes of this bench at this source hash; %s)" % (os.path.basename(pmc_csv(a.cfg)), stamp)
-                       if fresh_any else "none quoted: profiles/%s was taken from other kernel sources (%s; loaded library: srchash=%s) -- re-run bench_micro/pmc_bench.sh"
-                       % (os.path.basename(pmc_csv(a.cfg)), stamp or "absent", cur_hash))
         out = {
             "metric": "distinct k-mers/s reads->unitigs k=%d" % a.k,
             "value": total_distinct * a.steps / dt,
@@ -549,23 +698,17 @@ def main():
                        "exchange": xinfo,
                        "minimizer_size": st["minimizer_size"], "log2_partitions": st["log2_partitions"]},
             "counts": {x: st[x] for x in ("n_occurrences", "n_distinct", "n_solid", "n_pieces", "n_unitigs", "n_records", "n_big_partitions", "n_multipass_partitions", "n_cycles", "n_walked_unitigs")},
-            "checks": checks, "checks_passed": all(checks.values()),
-            "digest": {"set_digest": "%016x" % dig_last["set_digest"], "kc_sum": dig_last["kc_sum"], "kmers_in_unitigs": dig_last["kmers_in_unitigs"]},
-            "verify": verify_info,
-            "stage_ms": {x: acc[x] / a.steps for x in acc},
-            "roofline": {"bound": "hbm", "kernel": head["kernel"], "achieved": head["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": head["frac"],
-                         "traffic": head["traffic"], "traffic_source": traffic_src,
-                         "alg_bytes_per_launch": head["alg_bytes_per_launch"], "avg_launch_ms": head["avg_launch_ms"],
-                         "headline_rule": "of the stage kernels within 5 % of the longest: the lowest fraction",
-                         "kernels": kernels,
-                         "pipeline": {"alg_bytes": alg_total, "gpu_ms": gpu_ms,
-                                      "achieved": alg_total / (gpu_ms * 1e-3) / 1e9,
-                                      "frac": alg_total / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}},
         }
+        if a.full:
+            out.update({"checks": checks, "checks_passed": all(checks.values()),
+                        "digest": {"set_digest": "%016x" % dig_last["set_digest"], "kc_sum": dig_last["kc_sum"], "kmers_in_unitigs": dig_last["kmers_in_unitigs"]},
+                        "verify": verify_info})
+        out["stage_ms"] = {x: acc[x] / a.steps for x in acc}
+        if a.full:
+            out["roofline"] = roofline(a, st, acc)
     g.close(); g.release_cached()                            # (close() hands the buffers to the process's pool; release_cached() gives the HBM back to the driver: the
                                                              #  end-to-end leg is a child process and cannot drain this process's pool)
-    if rank == 0:
+    if rank == 0 and a.full:
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cb = cpu_baseline(a.k, a.abundance_min, a.read_len, gen_cfg, a.cpu_sample_reads)
             if "unitig_sets_equal" in cb:
@@ -588,8 +731,9 @@ def main():
             except Exception as ex:                          # (no scratch space, no CLI binary: the line still stands)
                 out["e2e"] = {"error": repr(ex)}; out["t_e2e_s"] = None
         out["checks_passed"] = all(out["checks"].values())
+    if rank == 0:
         json_out.write(json.dumps(out) + "\n"); json_out.flush()
-        if not out["checks_passed"]:
+        if a.full and not out["checks_passed"]:
             sys.stderr.write("bench.py: OUTPUT CHECK FAILED: %r\n" % out["checks"])
             sys.exit(3)
     if dist is not None:

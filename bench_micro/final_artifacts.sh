@@ -9,11 +9,11 @@ for c in 3 4 5; do
   cp $O/${tag}_pmc_hbm_traffic_per_kernel_cfg$c.csv $R/profiles/${rnd}_pmc_hbm_traffic_per_kernel_cfg$c.csv
 done
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/${tag}_bench_n1.json 2> $O/${tag}_bench_n1.err
-python bench.py --cfg 4 --steps 3 --warmup 1 > $O/${tag}_bench_cfg4_n1.json 2> $O/${tag}_bench_cfg4.err
-python bench.py --cfg 5 --steps 3 --warmup 1 --no-cpu-baseline > $O/${tag}_bench_cfg5_n1.json 2> $O/${tag}_bench_cfg5.err
-python bench.py --cfg 3 --skewed --steps 3 --warmup 1 > $O/${tag}_bench_cfg3_skewed.json 2> $O/${tag}_bench_cfg3_skewed.err
-HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --force-dist --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/${tag}_bench_forcedist_1rank.json 2> $O/${tag}_forcedist.err
+python bench.py --full --steps 20 --warmup 5 > $O/${tag}_bench_n1.json 2> $O/${tag}_bench_n1.err
+python bench.py --full --cfg 4 --steps 3 --warmup 1 > $O/${tag}_bench_cfg4_n1.json 2> $O/${tag}_bench_cfg4.err
+python bench.py --full --cfg 5 --steps 3 --warmup 1 --no-cpu-baseline > $O/${tag}_bench_cfg5_n1.json 2> $O/${tag}_bench_cfg5.err
+python bench.py --full --cfg 3 --skewed --steps 3 --warmup 1 > $O/${tag}_bench_cfg3_skewed.json 2> $O/${tag}_bench_cfg3_skewed.err
+HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --force-dist --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/${tag}_bench_forcedist_1rank.json 2> $O/${tag}_forcedist.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof -o p -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > $O/${tag}_prof.log 2>&1
 cp $O/${tag}_prof/p_kernel_stats.csv $O/${tag}_kernel_stats.csv

@@ -11,7 +11,7 @@ CDBG_LOG_NP=23 python bench_micro/hostile_timing.py 100000000 31 3 2>/dev/null >
 echo "# uniform config 3, default" >> $L
 python bench_micro/hostile_timing.py 100000000 31 3 3 2>/dev/null >> $L
 cat $L
-HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --force-dist --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/${tag}_bench_forcedist_1rank.json 2> $O/${tag}_forcedist.err
+HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --force-dist --steps 3 --warmup 1 --no-cpu-baseline --no-e2e > $O/${tag}_bench_forcedist_1rank.json 2> $O/${tag}_forcedist.err
 python - <<PY
 import json
 d=json.loads(open("$O/${tag}_bench_forcedist_1rank.json").read().strip().splitlines()[-1])

@@ -1,5 +1,6 @@
 """Binds the kernel-logic simulator (tests/hostsim/_build/libcdbg_hostsim.so).
 TEST INFRASTRUCTURE: same C ABI, same kernel source, workgroup threads as CPU fibers."""
+import fcntl
 import os
 import subprocess
 
@@ -15,5 +16,10 @@ def load():
     newest = max([os.path.getmtime(os.path.join(SRC, f)) for f in os.listdir(SRC)] + [os.path.getmtime(os.path.join(HOST, f)) for f in os.listdir(HOST)] +
                  [os.path.getmtime(os.path.join(HERE, "hostsim", f)) for f in ("hostsim.h", "build.sh")])
     if not os.path.exists(SO) or os.path.getmtime(SO) < newest:
-        subprocess.check_call([os.path.join(HERE, "hostsim", "build.sh")], stdout=subprocess.DEVNULL)
+        # one builder at a time (parallel pytest workers): a second one would rewrite bcalm_hostsim while the first one's tests run it
+        os.makedirs(os.path.dirname(SO), exist_ok=True)
+        with open(os.path.join(os.path.dirname(SO), ".lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if not os.path.exists(SO) or os.path.getmtime(SO) < newest:
+                subprocess.check_call([os.path.join(HERE, "hostsim", "build.sh")], stdout=subprocess.DEVNULL)
     return api.load(SO)

@@ -11,6 +11,7 @@ the HIP output, and of the real `bcalm` CLI binary (HIP build).
     src/bcalm_1.cpp:49-97) on FASTA, FASTQ.gz and file-list inputs.
 """
 import gzip
+import json
 import random
 import os
 import re
@@ -25,6 +26,7 @@ from parity import assert_parity, config2_genome
 pytestmark = pytest.mark.gpu
 ROOT = oracle_lib.ROOT
 EVAL = os.path.join(ROOT, "oracle", "_ref", "unitigEvaluator")
+REF_VERDICTS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_checker.json")))
 BCALM = os.path.join(ROOT, "bcalm_amd", "_build", "bcalm")
 
 
@@ -103,7 +105,15 @@ def _evaluator_verdict(tmp_path, unitigs, ref_records, k):
     return int(nums.group(1)), int(nums.group(2))
 
 
-@pytest.mark.skipif(not os.path.exists(EVAL), reason="oracle/_ref/unitigEvaluator not prebuilt (needs /root/reference at build time)")
+def _recorded_verdict(key, g, st):
+    """the checker's verdict recorded for this input (tests/golden/reference_checker.json): the unitigs of `g` must be the set it
+    judged (cdbg_digest has the formula of parity.set_digest), and it found every k-mer of the input once"""
+    rec = REF_VERDICTS[key]
+    assert "%016x" % g.digest()["set_digest"] == rec["set_digest"]
+    assert rec["in_ref"] == rec["tp"] == rec["solid"] == st["n_solid"] == st["n_distinct"]
+    assert rec["erroneous"] == rec["missing"] == 0 and not rec["repeated"]
+
+
 @pytest.mark.parametrize("k", [31, 32, 55, 96, 127])
 def test_reference_checker_accepts_hip_unitigs(oracle, hip, tmp_path, k):
     """the reference's own checker on the GPU output of the config-2 shape (4.64 Mbp genome with planted direct and
@@ -114,12 +124,16 @@ def test_reference_checker_accepts_hip_unitigs(oracle, hip, tmp_path, k):
     text = config2_genome(oracle)
     g = bcalm_amd.Graph(k, 1, lib=hip)
     g.push_text(text); g.run()
-    ut = g.unitigs(); st = g.stats(); assert_verified(g); g.close()
-    in_ref, tp = _evaluator_verdict(tmp_path, ut, [text.decode().strip()], k)
-    assert in_ref == tp == st["n_solid"] == st["n_distinct"]
+    ut = g.unitigs(); st = g.stats(); assert_verified(g)
+    real_genome = bool(os.environ.get("CDBG_ECOLI_FASTA"))       # (the recorded verdicts are of the synthetic genome)
+    if not real_genome:
+        _recorded_verdict("config2/%d" % k, g, st)
+    g.close()
+    if os.path.exists(EVAL) or real_genome:
+        in_ref, tp = _evaluator_verdict(tmp_path, ut, [text.decode().strip()], k)
+        assert in_ref == tp == st["n_solid"] == st["n_distinct"]
 
 
-@pytest.mark.skipif(not os.path.exists(EVAL), reason="oracle/_ref/unitigEvaluator not prebuilt (needs /root/reference at build time)")
 @pytest.mark.parametrize("k,n_reads,read_len,cfg", [(31, 150000, 150, 3 | 0x100), (55, 100000, 150, 4 | 0x100), (127, 12000, 1000, 5 | 0x100), (64, 12000, 1000, 5 | 0x100)])
 def test_reference_checker_on_hostile_reads(oracle, hip, tmp_path, k, n_reads, read_len, cfg):
     """the same verdict on READS of the hostile generator (low-complexity blocks, 1000 copies of a repeat, homopolymer runs,
@@ -129,9 +143,12 @@ def test_reference_checker_on_hostile_reads(oracle, hip, tmp_path, k, n_reads, r
     text = oracle.synth_reads(n_reads, read_len, cfg)
     g = bcalm_amd.Graph(k, 1, lib=hip)
     g.push_text(text); g.run()
-    ut = g.unitigs(); st = g.stats(); assert_verified(g); g.close()
-    in_ref, tp = _evaluator_verdict(tmp_path, ut, [r for r in text.decode().split("\n") if r], k)
-    assert in_ref == tp == st["n_solid"] == st["n_distinct"]
+    ut = g.unitigs(); st = g.stats(); assert_verified(g)
+    _recorded_verdict("hostile/%d/%d/%d/%d" % (k, n_reads, read_len, cfg), g, st)
+    g.close()
+    if os.path.exists(EVAL):
+        in_ref, tp = _evaluator_verdict(tmp_path, ut, [r for r in text.decode().split("\n") if r], k)
+        assert in_ref == tp == st["n_solid"] == st["n_distinct"]
 
 
 def test_against_a_real_bcalm_binary(oracle, hip):

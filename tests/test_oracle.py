@@ -125,21 +125,26 @@ def test_even_k_palindromic_kmer_is_its_own_unitig(oracle):
 
 
 EVAL = os.path.join(ROOT, "oracle", "_ref", "unitigEvaluator")
+REF_VERDICTS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_checker.json")))
 
 
-@pytest.mark.skipif(not os.path.exists(EVAL) and not os.path.exists("/root/reference/scripts/unitigEvaluator.cpp"),
-                    reason="reference checker neither prebuilt nor buildable here")
 @pytest.mark.parametrize("key", ["tiny_read/21/1", "minitip/21/1", "pufferize_refs/9/1", "circ_test2/7/1", "rand_c/21/1"])
 def test_reference_checker_accepts_oracle_unitigs(oracle, tmp_path, key):
     """the reference's own k-mer-set checker (scripts/unitigEvaluator.cpp:147-217):
     TP == all, FP == FN == 0, no 'REPEATED kmers' line.  abundance_min == 1 cases only
-    (the checker has no abundance notion)."""
-    if not os.path.exists(EVAL):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
+    (the checker has no abundance notion).  Its verdict on each input is recorded with the set digest of the unitigs it
+    judged (tests/golden/reference_checker.json, make_reference_checker_golden.py): the oracle's unitigs must be that set,
+    and where the checker is built (oracle/_ref/) it judges them again."""
+    from parity import set_digest
     name, k, amin = _case(key)
     assert amin == 1
     text = oracle_lib.read_input(name)
     got = oracle.run(text, k, amin)
+    rec = REF_VERDICTS["oracle/" + key]
+    assert rec["in_ref"] == rec["tp"] == got["stats"]["solid"] and rec["erroneous"] == rec["missing"] == 0 and not rec["repeated"]
+    assert "%016x" % set_digest(got["unitigs"]) == rec["set_digest"]
+    if not os.path.exists(EVAL):
+        return
     ref = tmp_path / "ref.fa"
     utg = tmp_path / "utg.fa"
     # the checker wants one-line-per-sequence FASTA and treats only 'N' as a break
