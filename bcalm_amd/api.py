@@ -14,6 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "_build", "libcdbg.so")
 
 
+E_NOMEM, E_INTERNAL = -3, -5                          # include/cdbg.h CDBG_E_NOMEM, CDBG_E_INTERNAL
+
+
 class CdbgError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libcdbg error {code}: {msg}")
@@ -285,8 +288,9 @@ class Graph:
         k-mer multiset of the unitigs == solid set (counts + two commutative sums), and no pair of unitig ends that are each
         other's only link (maximality).  mergeable_ends is None on a rank that holds a share of the unitigs.
         edges: also run the edge-conservation pass (verify_edges: a 12-byte x pow2(3 x n_solid) table).  A graph too large for that
-        pass (or a card without room for its table) reports edges = None -- with the reason under "edges_error" -- instead of failing
-        the k-mer-set / maximality verdict; edges=False skips the pass."""
+        pass (or a card without room for its table: CDBG_E_NOMEM) reports edges = None -- with the reason under "edges_error" -- instead
+        of failing the k-mer-set / maximality verdict; any other failure of the pass raises.  edges=False skips
+        the pass."""
         out = (C.c_uint64 * 8)()
         self._ck(self.lib.cdbg_verify(self._h, out))
         e, why = None, None
@@ -294,6 +298,8 @@ class Graph:
             try:
                 e = self.verify_edges()
             except CdbgError as ex:
+                if ex.code != E_NOMEM:
+                    raise
                 why = str(ex)
         d = self._verify_dict(out, e)
         if why is not None:

@@ -351,6 +351,9 @@ int count_impl(cdbg_ctx* c) {
     DeferPlan dp; uint32_t& defer_S = dp.n;                   // deferred placement: slices of the partition space (1: off) and their streams
     OvfParams var_op{};                                      // skewed inputs: the overflow-region layout (its finishing pass runs slice by slice under deferred placement)
     bool deferred_open = false;                              // placement kernels of this step are (or may be) still running: the record count and the spill list are not final
+    // (every return while they may still run -- an error between their launch and the wait for them below -- waits for them first: they write the
+    //  records, the fill counters and the spill list, which a retried count or a pooled buffer handed out again would share with them)
+    struct PlaceGuard { cdbg_ctx* c; const bool& open; ~PlaceGuard() { if (open && c->place_stream) (void)hipStreamSynchronize(c->place_stream); } } place_guard{ c, deferred_open };
     uint64_t sample_ns = 0, sample_stride = 0, sample_recs = 0;   // the capped path's sampled histogram, when it ran (still in part_count)
     if (c->ss_on) capped = true;                             // tiles [0, ss_done) were scanned while the input was arriving
     auto defer_fill_params = [&](ScanParams& q) {            // the slices and streams of dp as the kernels see them
@@ -703,8 +706,11 @@ int count_impl(cdbg_ctx* c) {
             // the capacity estimate was off by more than the spill list holds (the scan alone had not shown it): this step once more, every record placed by
             // the scan, which then falls back to the exact layout by itself
             HIPCK(hipMemset(c->derr.p, 0, 4 * sizeof(uint32_t))); HIPCK(hipMemset(c->cursors.p + 6, 0, sizeof(uint64_t)));
+            c->st.n_deferred_records = 0; c->st.ms_place = 0;   // (the statistics are those of the count that is kept, as when the scan alone shows the overflow)
             c->defer_off_once = true;
-            return count_impl<W>(c);
+            const int rc = count_impl<W>(c);
+            c->defer_off_once = false;                       // (consumed by the re-count's defer_plan -- or never looked at, when it took a layout without deferral)
+            return rc;
         }
         if (n_spill) CK(repair_spills(var ? c->ovf_words.p : nullptr));   // (the tier above left the spilled partitions alone; their gathered copies are counted below)
     }

@@ -384,7 +384,8 @@ int verify_edges_view(cdbg_ctx* c, const UnitigView& v, uint64_t n_links, uint64
     hipStream_t s = c->stream;
     const uint64_t n_home = c->st.n_solid;
     const uint64_t cap = pow2_at_least(3 * n_home + 1024);   // (at most 2 junctions per k-mer: never more than two thirds full)
-    if (cap > (1ull << 32)) return fail(CDBG_E_INTERNAL, "too many solid k-mers (%llu) for the 32-bit slots of the junction table", (unsigned long long)n_home);
+    // (a capacity limit like an allocation that fails, and reported as one: Graph.verify() then leaves the edges out instead of failing)
+    if (cap > (1ull << 32)) return fail(CDBG_E_NOMEM, "too many solid k-mers (%llu) for the 32-bit slots of the junction table", (unsigned long long)n_home);
     DBuf<uint64_t> jt_keys, d; DBuf<uint32_t> jt_cnt;
     CK(jt_keys.alloc(cap * W, false)); CK(jt_cnt.alloc(cap, false)); CK(d.alloc(4, true));
     HIPCK(hipMemsetAsync(jt_keys.p, 0xFF, cap * W * sizeof(uint64_t), s));

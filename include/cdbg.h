@@ -266,7 +266,10 @@ int cdbg_unitig_id_base(cdbg_ctx* ctx, uint64_t* first_id, uint64_t* total);
  *   CDBG_GLUE_LOG=1               junction records through the sequential log CDBG_GLUE_TABLE=1         global-table junction join
  *   CDBG_JOIN_LOG_JB=<n>          log2 of the join buckets (0 forces the overflow fallback)
  *   CDBG_FORCE_MULTI=1            run the multi-GPU data path with one rank   CDBG_STAGE_BYTES, CDBG_STREAM_MIN_BYTES, CDBG_STREAM_BATCH_TILES: ingest staging sizes
- *   CDBG_GLUE_REPLICATED=1        the replicated glue exchange for emit_replicated = 0 as well       CDBG_HOST_MARKS=1  wall-clock marks between host-side phases (stderr) */
+ *   CDBG_GLUE_REPLICATED=1        the replicated glue exchange for emit_replicated = 0 as well       CDBG_HOST_MARKS=1  wall-clock marks between host-side phases (stderr)
+ *   CDBG_POISON_ALLOC=<byte>      every device block newly obtained without a request for zeroing (fresh, or from the process's pool) is
+ *                                 filled with that byte (0xFF, 0xA5, ...): no kernel may depend on what a buffer held before.  Read for every
+ *                                 new block, never on the path that keeps an existing allocation */
 
 #ifdef __cplusplus
 }

@@ -223,9 +223,18 @@ inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-template <class T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+// CDBG_SIM_POISON=<byte> (tests): every new block is filled with that byte instead of what malloc hands out (fresh mmap pages
+// are zero, which would hide a kernel that reads a word it never wrote).  Read on every call, so that a test can set and unset it.
+namespace hostsim {
+inline void* poisoned(void* p, size_t n) {
+    const char* e = getenv("CDBG_SIM_POISON");
+    if (p && e && *e) memset(p, (int)(strtol(e, nullptr, 0) & 0xFF), n);
+    return p;
+}
+}  // namespace hostsim
+template <class T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)::hostsim::poisoned(malloc(n ? n : 1), n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-inline hipError_t hipHostMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+inline hipError_t hipHostMalloc(void** p, size_t n) { *p = ::hostsim::poisoned(malloc(n ? n : 1), n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t = 0) { memset(p, v, n); return hipSuccess; }
