@@ -48,7 +48,7 @@ EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
-           "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base",
+           "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -111,6 +111,7 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_num_links.argtypes = [vp, C.POINTER(u64)]
     lib.cdbg_fetch_links.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.cdbg_unitig_id_base.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.cdbg_load_unitigs.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -191,6 +192,24 @@ class Graph:
             acc += len(s)
         offs[len(seqs)] = acc
         self._ck(self.lib.cdbg_push_reads(self._h, b"".join(seqs), offs, len(seqs)))
+
+    def load_unitigs(self, seqs, kc=None):
+        """adopt a unitig set of the caller's (sequences as str / bytes in ACGTacgt, each at least k long; kc: one KC per sequence,
+        default all 0) as this fresh graph's resident unitigs (cdbg_load_unitigs): links() then joins them without a degree bound,
+        unitigs() / unitigs_packed() / digest() / stats() describe them; reset() forgets them"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = 0
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        kcs = None
+        if kc is not None:
+            if len(kc) != len(bs):
+                raise ValueError("kc: one value per sequence")
+            kcs = (C.c_uint64 * max(len(bs), 1))(*[int(x) for x in kc])
+        self._ck(self.lib.cdbg_load_unitigs(self._h, b"".join(bytes(b) for b in bs), off, len(bs), kcs))
 
     def generate_reads(self, n_reads, read_len, cfg, first_read=0, total_reads=None):
         total = n_reads if total_reads is None else total_reads

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "k_links.h"
+#include "k_relink.h"
 #include "k_verify.h"
 #include "k_dglue.h"
 #include "k_walk.h"
@@ -45,6 +46,7 @@ using namespace cdbg;
 #include "host_exchange.h"
 #include "host_glue_sharded.h"
 #include "host_glue.h"
+#include "host_relink.h"
 
 
 // =======================================================================================
@@ -110,6 +112,7 @@ int cdbg_release_cached(void) {
 
 int cdbg_push_reads(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
     if (!c || !bases || !offsets) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_push_reads"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage != 0 || c->reads_final) return fail(CDBG_E_STATE, "reads must be pushed before the first stage");
     std::lock_guard<std::mutex> lk(c->ingest_mu);
@@ -122,6 +125,7 @@ int cdbg_push_reads(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uin
 }
 int cdbg_push_text(cdbg_ctx* c, const char* text, uint64_t nbytes) {
     if (!c || (!text && nbytes)) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_push_text"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage != 0 || c->reads_final) return fail(CDBG_E_STATE, "reads must be pushed before the first stage");
     std::lock_guard<std::mutex> lk(c->ingest_mu);
@@ -131,6 +135,7 @@ int cdbg_push_text(cdbg_ctx* c, const char* text, uint64_t nbytes) {
 }
 int cdbg_stage_acquire(cdbg_ctx* c, char** buf, uint64_t* capacity) {
     if (!c || !buf || !capacity) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_stage_acquire"));
     (void)hipSetDevice(c->prm.device_id);                 // (any host thread: one parser thread per slice of the input)
     if (c->stage != 0 || c->reads_final) return fail(CDBG_E_STATE, "reads must be pushed before the first stage");
     std::lock_guard<std::mutex> lk(c->ingest_mu);
@@ -138,6 +143,7 @@ int cdbg_stage_acquire(cdbg_ctx* c, char** buf, uint64_t* capacity) {
 }
 int cdbg_stage_commit(cdbg_ctx* c, char* buf, uint64_t nbytes) {
     if (!c || !buf) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_stage_commit"));
     (void)hipSetDevice(c->prm.device_id);
     if (c->stage != 0 || c->reads_final) return fail(CDBG_E_STATE, "reads must be pushed before the first stage");
     std::lock_guard<std::mutex> lk(c->ingest_mu);
@@ -145,6 +151,7 @@ int cdbg_stage_commit(cdbg_ctx* c, char* buf, uint64_t nbytes) {
 }
 int cdbg_expect_input(cdbg_ctx* c, uint64_t text_bytes) {
     if (!c) return fail(CDBG_E_PARAM, "null context");
+    CK(refuse_loaded(c, "cdbg_expect_input"));
     // (a text that is complete already -- cdbg_generate_reads -- must not be announced again: the pre-warm thread would swap the buffer that holds it)
     if (c->stage != 0 || c->n_dev || c->pin_fill || c->reads_final) return fail(CDBG_E_STATE, "cdbg_expect_input must precede the first push");
     c->expect_bytes = text_bytes;
@@ -162,6 +169,7 @@ int cdbg_expect_input(cdbg_ctx* c, uint64_t text_bytes) {
 }
 int cdbg_generate_reads(cdbg_ctx* c, uint64_t first_read, uint64_t n_reads, uint64_t total_reads, uint64_t read_len, int cfg) {
     if (!c) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_generate_reads"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage != 0 || c->reads_final || c->n_dev || c->pin_fill) return fail(CDBG_E_STATE, "reads already present");
     if (!n_reads || !read_len || total_reads < n_reads) return fail(CDBG_E_PARAM, "bad synthetic read set");
@@ -179,6 +187,7 @@ int cdbg_generate_reads(cdbg_ctx* c, uint64_t first_read, uint64_t n_reads, uint
 }
 int cdbg_read_text(cdbg_ctx* c, uint64_t first_byte, uint64_t nbytes, char* out) {
     if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_read_text"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     CK(upload_pending(c));
     if (first_byte + nbytes > c->nbytes) return fail(CDBG_E_PARAM, "range beyond the resident text");
@@ -204,6 +213,7 @@ int cdbg_read_text(cdbg_ctx* c, uint64_t first_byte, uint64_t nbytes, char* out)
 static int count_dispatch(cdbg_ctx* c) { DISPATCH_W(count_impl) }
 int cdbg_count(cdbg_ctx* c) {
     if (!c) return fail(CDBG_E_PARAM, "null context");
+    CK(refuse_loaded(c, "cdbg_count"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage != 0) return fail(CDBG_E_STATE, "cdbg_count called twice");
     CK(count_dispatch(c));
@@ -232,10 +242,21 @@ int cdbg_count(cdbg_ctx* c) {
     }
     return CDBG_OK;
 }
-int cdbg_compact(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(compact_impl) }
-int cdbg_glue(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(glue_impl) }
-int cdbg_run(cdbg_ctx* c) { CK(cdbg_count(c)); CK(cdbg_compact(c)); return cdbg_glue(c); }
-int cdbg_link(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(link_impl) }
+int cdbg_compact(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); CK(refuse_loaded(c, "cdbg_compact")); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(compact_impl) }
+int cdbg_glue(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); CK(refuse_loaded(c, "cdbg_glue")); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(glue_impl) }
+int cdbg_run(cdbg_ctx* c) { CK(refuse_loaded(c, "cdbg_run")); CK(cdbg_count(c)); CK(cdbg_compact(c)); return cdbg_glue(c); }
+static int relink_dispatch(cdbg_ctx* c) { DISPATCH_W(relink_impl) }
+int cdbg_link(cdbg_ctx* c) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    if (c->loaded) return relink_dispatch(c);                // a set the caller supplied: the join without a degree bound (k_relink.h)
+    DISPATCH_W(link_impl)
+}
+int cdbg_load_unitigs(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_unitigs, const uint64_t* kc) {
+    if (!c || !offsets || (!bases && n_unitigs)) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    return load_unitigs_impl(c, bases, offsets, n_unitigs, kc);
+}
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
@@ -260,7 +281,7 @@ int cdbg_reset(cdbg_ctx* c) {
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     prewarm_join(c);
     if (c->place_stream) (void)hipStreamSynchronize(c->place_stream);   // (a count stage that returned with an error may have left its placement stream busy)
-    c->stage = 0; c->st = cdbg_stats_t{};
+    c->stage = 0; c->loaded = false; c->st = cdbg_stats_t{};
     c->n_solid_entries = c->n_pieces = c->n_piece_bases = c->n_unitigs = c->unitig_total = 0; c->linked = false; c->n_links = 0; c->joined = false;
     c->xchg_done = false; c->xp_ab_ready = false; c->comm_bytes = 0; c->piece_lo = c->piece_hi = 0; c->ss_on = false; c->expect_bytes = 0;
     return CDBG_OK;                                  // reads and every device buffer stay resident
@@ -268,12 +289,14 @@ int cdbg_reset(cdbg_ctx* c) {
 
 int cdbg_num_solid(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_num_solid"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage < 1) return fail(CDBG_E_STATE, "cdbg_num_solid before cdbg_count");
     *n = c->st.n_solid; return CDBG_OK;
 }
 int cdbg_fetch_solid(cdbg_ctx* c, char* kmers, uint32_t* counts, uint64_t capacity, uint64_t* n_written) {
     if (!c || !kmers || !counts || !n_written) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_fetch_solid"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage < 1) return fail(CDBG_E_STATE, "cdbg_fetch_solid before cdbg_count");
     if (capacity < c->st.n_solid) return fail(CDBG_E_PARAM, "capacity %llu < %llu solid k-mers", (unsigned long long)capacity, (unsigned long long)c->st.n_solid);
@@ -346,6 +369,7 @@ int cdbg_fetch_unitigs_packed(cdbg_ctx* c, uint8_t* packed, uint64_t packed_capa
 }
 int cdbg_fetch_unitig_abundances(cdbg_ctx* c, uint64_t first, uint64_t n, uint32_t* ab, uint64_t* ab_off) {
     if (!c || !ab || !ab_off) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_fetch_unitig_abundances"));
     (void)hipSetDevice(c->prm.device_id);                 // (the caller may be any host thread: one thread per GPU in the CLI)
     if (c->stage < 3) return fail(CDBG_E_STATE, "cdbg_fetch_unitig_abundances before cdbg_glue");
     if (!c->prm.all_abundance_counts) return fail(CDBG_E_STATE, "context was created without all_abundance_counts");
@@ -404,23 +428,27 @@ int cdbg_digest(cdbg_ctx* c, uint64_t out[4]) {
     DigestParams dp{ c->n_unitigs, c->k, c->unitig_off.p, c->unitig_len.p, c->unitig_kc.p, c->unitig_bases.p,
                      c->seg_off.p, c->seg_n.p, c->solid_cnt.p, c->n_local_parts, d.p };
     if (c->n_unitigs) CDBG_LAUNCH(k_digest_unitigs, std::min<uint64_t>((c->n_unitigs + 255) / 256, 1u << 16), 256, c->stream, dp);
-    CDBG_LAUNCH(k_digest_solid, std::min<uint64_t>((c->n_local_parts + 255) / 256, 1u << 16), 256, c->stream, dp);
+    if (!c->loaded) CDBG_LAUNCH(k_digest_solid, std::min<uint64_t>((c->n_local_parts + 255) / 256, 1u << 16), 256, c->stream, dp);
     HIPCK(hipStreamSynchronize(c->stream));
     CK(read_u64(d.p, out, 4));
+    if (c->loaded) out[1] = ~0ull;                           // (a loaded set: no k-mers were counted)
     return CDBG_OK;
 }
 int cdbg_verify(cdbg_ctx* c, uint64_t out[8]) {
     if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_verify"));
     (void)hipSetDevice(c->prm.device_id);
     DISPATCH_WA(verify_impl, c, out)
 }
 int cdbg_verify_edges(cdbg_ctx* c, uint64_t out[4]) {
     if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_verify_edges"));
     (void)hipSetDevice(c->prm.device_id);
     DISPATCH_WA(verify_edges_impl, c, out)
 }
 int cdbg_verify_unitigs(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_unitigs, uint64_t out[12]) {
     if (!c || !out || !offsets || (!bases && n_unitigs)) return fail(CDBG_E_PARAM, "null argument");
+    CK(refuse_loaded(c, "cdbg_verify_unitigs"));
     (void)hipSetDevice(c->prm.device_id);
     DISPATCH_WA(verify_unitigs_impl, c, bases, offsets, n_unitigs, out)
 }

@@ -235,6 +235,7 @@ struct cdbg_ctx {
     uint64_t n_local_parts = 1;
     hipStream_t stream{};
     int stage = 0;                               // 0 input, 1 counted, 2 compacted, 3 glued
+    bool loaded = false;                         // stage 3 by cdbg_load_unitigs: the resident unitigs are the caller's; no reads, no solid k-mers, no pieces (host_relink.h)
     cdbg_stats_t st{};
 
     // Ingest: pushed bytes go through two pinned staging buffers and are copied to the device asynchronously on

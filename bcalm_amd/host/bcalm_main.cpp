@@ -7,6 +7,9 @@
 //     (-version / -v), :39-48 (error -> "EXCEPTION: ..." on stdout, exit code 1),
 //     README.md:45-50 (FASTA/FASTQ, gzipped or not, or a file listing input files),
 //     README.md:62-72 (>id LN:i: KC:i: km:f: header), scripts/convertToGFA.py:74,36-49 (GFA).
+//   ./bcalm -in <prefix>.h5 -kmer-size 31 -skip-bcalm -skip-bglue -redo-links [-gfa]
+//     scripts/pufferize.py:61,143 and split_unitigs.py: their pieces carry no links; this mode reads <prefix>.unitigs.fa,
+//     recomputes the L: tokens of its records (cdbg_load_unitigs + cdbg_link) and rewrites the file in place.
 // Everything between parsing and writing is three calls into libcdbg.so (include/cdbg.h):
 // this file is the replacement for bcalm_1::execute()/Functor (src/bcalm_1.cpp:49-97).
 #include <zlib.h>
@@ -45,6 +48,7 @@ struct Options {
     std::string in, out;
     int k = 31, amin = 2, m = 0, device = 0, log_np = -1, n_gpus = 1, cores = 0;
     bool gfa = false, verbose = false, all_ab = false, no_stream = false;
+    bool redo_links = false, skip_bcalm = false, skip_bglue = false;   // -redo-links: only the link step, on an existing <prefix>.unitigs.fa
     std::string solid_out;
 };
 
@@ -67,6 +71,9 @@ Options parse(int argc, char** argv) {
         else if (a == "-log2-partitions") o.log_np = atoi(need("-log2-partitions"));
         else if (a == "-nb-gpus") o.n_gpus = atoi(need("-nb-gpus"));   // the GPU path's counterpart of -nb-cores: GPUs of this node (power of two)
         else if (a == "-gfa") o.gfa = true;
+        else if (a == "-redo-links") o.redo_links = true;             // the reference's hidden option: scripts/pufferize.py:143 tells its users to run it
+        else if (a == "-skip-bcalm") o.skip_bcalm = true;
+        else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
         else if (a == "-all-abundance-counts") o.all_ab = true;        // README.md:74-80
         else if (a == "-solid-kmers-out") o.solid_out = need("-solid-kmers-out");   // hidden in the reference (bcalm_1.cpp:37)
@@ -462,6 +469,172 @@ bool looks_like_file_list(const std::string& path) {       // README.md:47-50 "l
 
 void check(int rc) { if (rc != 0) throw std::runtime_error(cdbg_last_error()); }
 
+// ---- -redo-links: the link step alone, on the records of an existing <prefix>.unitigs.fa (any FASTA: sequences may wrap) ----
+struct FaRecord { std::string rest; size_t seq_off = 0, seq_len = 0; };   // rest: the header after its first word; the sequence lies in the slice's `bases`
+struct FaSlice { std::vector<FaRecord> recs; std::string bases; };
+void parse_unitig_slice(const char* p, const char* end, FaSlice& out) {
+    bool have = false;
+    while (p < end) {
+        const size_t n = line_len(p, end), m = rstrip_cr(p, n);
+        if (m && p[0] == '>') {
+            FaRecord r; r.seq_off = out.bases.size();
+            const char* sp = (const char*)memchr(p, ' ', m);
+            if (sp) r.rest.assign(sp + 1, (size_t)(p + m - sp - 1));
+            out.recs.push_back(std::move(r)); have = true;
+        } else if (m && p[0] != ';' && have) {
+            size_t a = 0, b = m;                                   // (blanks around a sequence line are not bases)
+            while (a < b && (p[a] == ' ' || p[a] == '\t')) ++a;
+            while (b > a && (p[b - 1] == ' ' || p[b - 1] == '\t')) --b;
+            out.bases.append(p + a, b - a); out.recs.back().seq_len += b - a;
+        } else if (m && p[0] != ';') usage_error("sequence data before the first '>' header");
+        p += n + 1;
+    }
+}
+// header tokens to keep: everything after the first word but the L: tokens, in order (tokens are separated by single blanks, as scripts/convertToGFA.py:77 splits them)
+void kept_tokens(const std::string& rest, std::vector<std::string>& out) {
+    out.clear();
+    size_t p = 0;
+    while (p <= rest.size()) {
+        size_t q = rest.find(' ', p); if (q == std::string::npos) q = rest.size();
+        if (q > p && rest.compare(p, 2, "L:") != 0) out.emplace_back(rest, p, q - p);
+        p = q + 1;
+    }
+}
+int redo_links(const Options& o, const std::string& prefix, int threads) {
+    auto t0 = std::chrono::steady_clock::now();
+    const std::string fa = prefix + ".unitigs.fa";
+    auto mp = std::make_shared<Mapped>();
+    { struct stat sb; if (stat(fa.c_str(), &sb) != 0) usage_error("-redo-links: cannot open " + fa + " (the unitigs of an earlier run are expected there)"); }
+    std::vector<FaSlice> slices;
+    if (mp->open(fa)) {                                            // (false: an empty file -- no records)
+        const char* p = mp->p; const size_t n = mp->n;
+        size_t slice = std::max<size_t>(n / (size_t)(threads * 4) + 1, 8u << 20);
+        if (const char* e = getenv("BCALM_SLICE_BYTES")) slice = std::max<size_t>(1, strtoull(e, nullptr, 10));
+        std::vector<std::pair<size_t, size_t>> cuts;
+        for (size_t beg = 0; beg < n;) {
+            size_t end = beg + slice >= n ? n : next_fasta_record(p, n, beg + slice);
+            if (end <= beg) end = n;
+            cuts.emplace_back(beg, end); beg = end;
+        }
+        slices.resize(cuts.size());
+        std::mutex em; std::string err;
+        pgz::parallel_for(cuts.size(), threads, [&](size_t i) {
+            try { parse_unitig_slice(p + cuts[i].first, p + cuts[i].second, slices[i]); }
+            catch (const std::exception& e) { std::lock_guard<std::mutex> l(em); if (err.empty()) err = e.what(); }
+        });
+        if (!err.empty()) usage_error(fa + ": " + err);
+    }
+    // records in file order: one arena, offsets, the headers
+    uint64_t nu = 0, tb = 0;
+    for (const FaSlice& sl : slices) { nu += sl.recs.size(); tb += sl.bases.size(); }
+    std::unique_ptr<char[]> seq(new char[tb + 1]);
+    std::vector<uint64_t> off(nu + 1, 0); std::vector<const std::string*> rest(nu ? nu : 1, nullptr);
+    {
+        uint64_t i = 0, w = 0;
+        for (const FaSlice& sl : slices) {
+            if (!sl.bases.empty()) memcpy(seq.get() + w, sl.bases.data(), sl.bases.size());
+            for (const FaRecord& r : sl.recs) {
+                if (r.seq_len < (size_t)o.k) usage_error(fa + ": record " + std::to_string(i) + " has " + std::to_string(r.seq_len) + " bases, fewer than k = " + std::to_string(o.k));
+                off[i] = w + r.seq_off; rest[i] = &r.rest; ++i;
+            }
+            w += sl.bases.size();
+        }
+        off[nu] = tb;
+    }
+    cdbg_params prm{}; prm.k = o.k; prm.abundance_min = std::max(1, o.amin); prm.minimizer_size = 0; prm.log2_partitions = -1; prm.device_id = o.device; prm.world_size = 1;
+    cdbg_ctx* ctx = nullptr; check(cdbg_create(&prm, &ctx));
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    if (cdbg_load_unitigs(ctx, seq.get(), off.data(), nu, nullptr) != 0) {
+        const std::string e = cdbg_last_error(); unsigned long long u = 0;
+        if (sscanf(e.c_str(), "unitig %llu", &u) == 1) usage_error(fa + ": record " + std::to_string(u) + ": " + e);
+        usage_error(fa + ": " + e);
+    }
+    check(cdbg_link(ctx));
+    uint64_t nl = 0; check(cdbg_num_links(ctx, &nl));
+    std::vector<uint64_t> loff(2 * nu + 1), kc(nu ? nu : 1); std::vector<uint32_t> lto(nl ? nl : 1);
+    check(cdbg_fetch_links(ctx, loff.data(), lto.data()));
+    { uint64_t n2 = 0, t2 = 0; check(cdbg_num_unitigs(ctx, &n2, &t2)); if (n2 != nu || t2 != tb) usage_error("internal: the loaded set differs from the file");
+      check(cdbg_fetch_unitigs(ctx, 0, nu, seq.get(), off.data(), kc.data())); }                       // (the library's copy: upper case)
+    // written beside the original and renamed over it: a failure leaves the file as it was
+    const std::string gfa_name = prefix + ".unitigs.gfa";
+    struct TmpOut {                                                // a temporary file: closed and removed on every way out but commit()
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+        void open(const std::string& n) { f = fopen(n.c_str(), "w"); if (!f) usage_error("cannot write " + n); name = n; }
+        bool close() { FILE* g = f; f = nullptr; return !g || fclose(g) == 0; }
+        bool commit(const std::string& to) { if (rename(name.c_str(), to.c_str()) != 0) return false; name.clear(); return true; }
+    } tfa, tgfa;
+    tfa.open(fa + ".tmp" + std::to_string((long)getpid()));
+    if (o.gfa) tgfa.open(gfa_name + ".tmp" + std::to_string((long)getpid()));
+    FILE* const out = tfa.f; FILE* const gfa = tgfa.f;
+    if (gfa) fprintf(gfa, "H\tVN:Z:1.0\tks:i:%d\n", o.k);
+    bool wfail = false; std::string werr;
+    {
+        const uint64_t BLOCK = 1u << 15, nblocks = (nu + BLOCK - 1) / BLOCK;
+        std::atomic<uint64_t> next_block{0};
+        std::mutex wm; std::condition_variable wcv; uint64_t turn = 0;
+        std::atomic<bool> stop{false};
+        auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+        auto write_blocks = [&]() {
+            std::string fb, gb; std::vector<std::string> toks;
+            for (;;) {
+                const uint64_t b = next_block.fetch_add(1);
+                if (b >= nblocks || stop.load()) break;
+                fb.clear(); gb.clear();
+                const uint64_t i0 = b * BLOCK, i1 = std::min(nu, i0 + BLOCK);
+                for (uint64_t i = i0; i < i1; ++i) {
+                    const uint64_t len = off[i + 1] - off[i];
+                    kept_tokens(*rest[i], toks);
+                    fb.push_back('>'); put_u(fb, i);                // consecutive renumbering, as the split scripts number their pieces
+                    for (const std::string& t : toks) { fb.push_back(' '); fb.append(t); }
+                    if (gfa) {                                      // the S line of scripts/convertToGFA.py:35-47 for this header
+                        gb.append("S\t"); put_u(gb, i); gb.push_back('\t'); gb.append(seq.get() + off[i], (size_t)len);
+                        for (const std::string& t : toks) { gb.push_back('\t'); if (t.compare(0, 2, "MA") == 0) { gb.append("MA:f:"); gb.append(t, 2, std::string::npos); } else gb.append(t); }
+                        while (!gb.empty() && strchr(" \t\r\f\v", gb.back())) gb.pop_back();
+                        gb.push_back('\n');
+                    }
+                    for (int side = 1; side >= 0; --side)          // '+' links (through the last k-mer) first, then '-'; targets ascending
+                        for (uint64_t j = loff[2 * i + side]; j < loff[2 * i + side + 1]; ++j) {
+                            const char fs = side ? '+' : '-', ts = (lto[j] & 1u) ? '-' : '+';
+                            fb.append(" L:"); fb.push_back(fs); fb.push_back(':'); put_u(fb, lto[j] >> 1); fb.push_back(':'); fb.push_back(ts);
+                            if (gfa) { gb.append("L\t"); put_u(gb, i); gb.push_back('\t'); gb.push_back(fs); gb.push_back('\t'); put_u(gb, lto[j] >> 1);
+                                       gb.push_back('\t'); gb.push_back(ts); gb.push_back('\t'); put_u(gb, (unsigned long long)(o.k - 1)); gb.append("M\n"); }
+                        }
+                    fb.append(" \n");
+                    fb.append(seq.get() + off[i], (size_t)len); fb.push_back('\n');
+                }
+                std::unique_lock<std::mutex> l(wm);
+                wcv.wait(l, [&] { return turn == b || stop.load(); });
+                if (stop.load()) break;
+                if (fwrite(fb.data(), 1, fb.size(), out) != fb.size()) wfail = true;
+                if (gfa && fwrite(gb.data(), 1, gb.size(), gfa) != gb.size()) wfail = true;
+                ++turn; wcv.notify_all();
+            }
+        };
+        auto writer = [&]() {                                      // (an exception must not leave its thread: the others wait for this one's turn)
+            try { write_blocks(); }
+            catch (const std::exception& e) { std::lock_guard<std::mutex> l(wm); if (werr.empty()) werr = e.what(); stop.store(true); wcv.notify_all(); }
+        };
+        const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)threads, nblocks));
+        std::vector<std::thread> th;
+        for (int i = 1; i < nt; ++i) th.emplace_back(writer);
+        writer();
+        for (auto& t : th) t.join();
+    }
+    if (!werr.empty()) usage_error("writing " + fa + ": " + werr);
+    if (!tfa.close()) wfail = true;
+    if (!tgfa.close()) wfail = true;
+    if (wfail) usage_error("write error on " + tfa.name + (o.gfa ? " or " + tgfa.name : ""));
+    mp.reset();                                                    // (unmap before the file is replaced)
+    // the GFA first: whatever fails up to here, or in this rename, leaves <prefix>.unitigs.fa as it was
+    if (o.gfa && !tgfa.commit(gfa_name)) usage_error("cannot rename " + tgfa.name + " to " + gfa_name);
+    if (!tfa.commit(fa)) usage_error("cannot rename " + tfa.name + " to " + fa + (o.gfa ? " (" + gfa_name + " is already the new one)" : ""));
+    printf("links recomputed: %llu unitigs, %llu links (%.2f s)\n", (unsigned long long)nu, (unsigned long long)nl,
+           std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    printf("unitigs written to %s\n", fa.c_str());
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -473,7 +646,18 @@ int main(int argc, char** argv) {
         Options o = parse(argc, argv);
         printf("BCALM 2 CLI, MI355X-native engine, version %s\n", CDBG_VERSION);
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
-        const std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
+        std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
+        if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
+        if (o.redo_links) {
+            if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
+            const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
+            if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
+                const size_t sl = o.in.find_last_of('/');
+                prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
+            }
+            int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            return redo_links(o, prefix, std::max(1, std::min(threads, 60)));
+        }
         auto t0 = std::chrono::steady_clock::now();
 
         if (o.n_gpus < 1 || (o.n_gpus & (o.n_gpus - 1))) usage_error("-nb-gpus must be a power of two");

@@ -214,8 +214,16 @@ int split_main(bool puffer, int argc, char** argv) {
     }
     fclose(s.out);
     printf("done. result is in: %s\n", outname.c_str());
-    printf("to get a GFA file with links for the split unitigs, re-run the link step on them and then:\n");
-    printf("bcalm_tools convertToGFA %s %s.gfa %zu\n", unitigs.c_str(), unitigs.c_str(), s.k);
+    // (the script's hint, scripts/pufferize.py:138-144, with this project's commands: the pieces are the ones split_unitigs writes as FASTA, and
+    //  they carry no links until the link step has run on them)
+    const std::string sfx = ".unitigs.fa";
+    const bool named = unitigs.size() > sfx.size() && unitigs.compare(unitigs.size() - sfx.size(), sfx.size(), sfx) == 0;
+    // (-redo-links looks for <prefix>.unitigs.fa in the working directory: the pieces are moved there under the file's own name)
+    const std::string target = named ? unitigs.substr(unitigs.find_last_of('/') == std::string::npos ? 0 : unitigs.find_last_of('/') + 1) : "[prefix].unitigs.fa";
+    printf("to get a FASTA file with links and a GFA file with links for the split unitigs, run:\n");
+    printf("bcalm_tools split_unitigs %s %s %zu\n", references.c_str(), unitigs.c_str(), s.k);
+    printf("mv %s.split.fa %s\n", unitigs.c_str(), target.c_str());
+    printf("bcalm -in %s -kmer-size %zu -skip-bcalm -skip-bglue -redo-links -gfa\n", target.c_str(), s.k);
     return 0;
 }
 

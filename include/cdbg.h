@@ -256,6 +256,24 @@ int cdbg_fetch_links(cdbg_ctx* ctx, uint64_t* end_off, uint32_t* link_to);
  * context's unitigs.  After cdbg_link. */
 int cdbg_unitig_id_base(cdbg_ctx* ctx, uint64_t* first_id, uint64_t* total);
 
+/* A unitig set SUPPLIED BY THE CALLER becomes the context's resident set, so that its links can be recomputed (the `bcalm -redo-links`
+ * mode: pieces cut by split_unitigs / pufferize, whose old links are void; the FASTA of any other program).  Host ASCII: sequence i is
+ * bases[offsets[i] .. offsets[i+1]) in ACGTacgt, stored upper-case; every length in [k, 2^32 - 1]; n_unitigs <= 2^31 - 1 (32-bit end ids);
+ * kc[n_unitigs] = the KC to keep with each sequence, NULL: all 0.  The bases are checked on the device.  The context must be fresh: no
+ * reads pushed or announced, no stage run, world_size == 1 (CDBG_E_STATE otherwise); a bad length or base is CDBG_E_PARAM and the message
+ * names the unitig and the byte.
+ * Afterwards the context is as after cdbg_glue for cdbg_num_unitigs, cdbg_fetch_unitigs, cdbg_fetch_unitigs_packed, cdbg_link,
+ * cdbg_num_links, cdbg_fetch_links, cdbg_unitig_id_base (0 and n) and cdbg_stats (n_unitigs, unitig_bases); cdbg_digest reports out[0],
+ * out[2], out[3] and out[1] = UINT64_MAX (no k-mers were counted).  Every call that needs reads, counted k-mers or pieces -- the push,
+ * stage and generate calls, cdbg_count / _compact / _glue / _run, cdbg_num_solid, cdbg_fetch_solid, cdbg_fetch_unitig_abundances, the
+ * cdbg_verify family -- returns CDBG_E_STATE until cdbg_reset forgets the set.
+ * cdbg_link on a loaded context joins WITHOUT a degree bound (bcalm_amd/csrc/k_relink.h): the sequences need not be the unitigs of one
+ * graph -- repeated records, self-loops, palindromic (k-1)-mers, any number of ends on one junction.  link_to of every end is in
+ * ascending order and the same bytes on every run; the number of links may exceed 2^32; what does not fit in memory is CDBG_E_NOMEM,
+ * and so is a set of more than (2^31 - 64) / 3 = 715 827 861 sequences: the load accepts it, cdbg_link cannot address its junction table
+ * (at most 2^31 slots, one key per end at two thirds full). */
+int cdbg_load_unitigs(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_unitigs, const uint64_t* kc);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
