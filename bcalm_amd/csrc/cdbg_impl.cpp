@@ -195,21 +195,6 @@ int cdbg_read_text(cdbg_ctx* c, uint64_t first_byte, uint64_t nbytes, char* out)
     return CDBG_OK;
 }
 
-#if CDBG_MAX_W >= 8
-#define DISPATCH_WIDE(fn, ...) case 5: return fn<5>(__VA_ARGS__); case 6: return fn<6>(__VA_ARGS__); case 7: return fn<7>(__VA_ARGS__); case 8: return fn<8>(__VA_ARGS__);
-#else
-#define DISPATCH_WIDE(fn, ...)
-#endif
-#define DISPATCH_WA(fn, ...)                                         \
-    switch (c->W) {                                                  \
-        case 1: return fn<1>(__VA_ARGS__);                           \
-        case 2: return fn<2>(__VA_ARGS__);                           \
-        case 3: return fn<3>(__VA_ARGS__);                           \
-        case 4: return fn<4>(__VA_ARGS__);                           \
-        DISPATCH_WIDE(fn, __VA_ARGS__)                               \
-        default: return fail(CDBG_E_PARAM, "k-mers of %d words: rebuild with CDBG_MAX_W", c->W);   \
-    }
-#define DISPATCH_W(fn) DISPATCH_WA(fn, c)
 static int count_dispatch(cdbg_ctx* c) { DISPATCH_W(count_impl) }
 int cdbg_count(cdbg_ctx* c) {
     if (!c) return fail(CDBG_E_PARAM, "null context");

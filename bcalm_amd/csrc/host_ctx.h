@@ -153,6 +153,22 @@ constexpr int TS_COMPACT_1 = CDBG_TSK1, TS_COMPACT_2 = 512, TS_COMPACT_4 = 512;
 #ifndef CDBG_MAX_W
 #define CDBG_MAX_W 8
 #endif
+// fn<W>(...) for the context's k-mer width
+#if CDBG_MAX_W >= 8
+#define DISPATCH_WIDE(fn, ...) case 5: return fn<5>(__VA_ARGS__); case 6: return fn<6>(__VA_ARGS__); case 7: return fn<7>(__VA_ARGS__); case 8: return fn<8>(__VA_ARGS__);
+#else
+#define DISPATCH_WIDE(fn, ...)
+#endif
+#define DISPATCH_WA(fn, ...)                                         \
+    switch (c->W) {                                                  \
+        case 1: return fn<1>(__VA_ARGS__);                           \
+        case 2: return fn<2>(__VA_ARGS__);                           \
+        case 3: return fn<3>(__VA_ARGS__);                           \
+        case 4: return fn<4>(__VA_ARGS__);                           \
+        DISPATCH_WIDE(fn, __VA_ARGS__)                               \
+        default: return fail(CDBG_E_PARAM, "k-mers of %d words: rebuild with CDBG_MAX_W", c->W);   \
+    }
+#define DISPATCH_W(fn) DISPATCH_WA(fn, c)
 template <int W> struct Cfg { static constexpr int TSC = 1024, TSK = 256, TSK2 = 512, NTC = 512, TSW = 128, TSW2 = 256; };
 // TSW: slots of the wave-per-bucket compaction tier (buckets of at most TSW / 2 entries; k_compact_wave.h)
 template <> struct Cfg<1> { static constexpr int TSC = TS_COUNT_1, TSK = TS_COMPACT_1, TSK2 = 2 * TS_COMPACT_1, NTC = CDBG_NTC1, TSW = 512, TSW2 = 1024; };   // (TSW2: the second wave tier, buckets of 257 .. 512 entries: round 5)
@@ -267,7 +283,7 @@ struct cdbg_ctx {
     // deferred record placement (host_count.h): the record streams of the slices the scan does not place itself, their cursors, the stream the
     // placement kernels run on beside the count stage, and one event per slice (+ [0]: where that stream's work of this step begins)
     DBuf<uint64_t> defer_recs; DBuf<uint32_t> defer_part, defer_count;
-    hipStream_t place_stream{}; hipEvent_t place_ev[17] = {}; hipEvent_t scan_ev{}; bool defer_off_once = false;
+    hipStream_t place_stream{}; hipEvent_t place_ev[17] = {}; hipEvent_t scan_ev{};
     DBuf<uint64_t> solid_keys; DBuf<uint32_t> solid_cnt; DBuf<uint64_t> solid_cursor, seg_off; DBuf<uint32_t> seg_n;
     DBuf<uint32_t> big_list, big_count, big_list2, big_count2, retry_list;
     uint64_t n_solid_entries = 0;                // home + traveller solid entries

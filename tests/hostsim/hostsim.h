@@ -9,6 +9,7 @@
 // Workgroups run one after another; `static` stands in for __shared__.
 #pragma once
 #include <ucontext.h>
+#include <unistd.h>
 
 #include <chrono>
 #include <cstdint>
@@ -16,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -141,6 +143,13 @@ inline void run_block(unsigned bx, unsigned nthreads, const std::function<void()
 template <class F>
 inline void launch(unsigned grid, unsigned block, F f) {
     std::function<void()> body = f;
+    // CDBG_SIM_TRACE=<file> (dev aid, no test depends on it): one line per launch -- kernel text, grid, block -- appended to that file;
+    // "%p" in the name becomes the process id (one file per rank of a multi-process test)
+    if (const char* e = getenv("CDBG_SIM_TRACE")) if (*e) {
+        std::string name(e);
+        if (const size_t at = name.find("%p"); at != std::string::npos) name.replace(at, 2, std::to_string((long)getpid()));
+        if (FILE* fp = fopen(name.c_str(), "a")) { fprintf(fp, "%s, %u, %u\n", g_kernel_name, grid, block); fclose(fp); }
+    }
     g_gridDim.x = grid; g_blockDim.x = block;
     for (unsigned b = 0; b < grid; ++b) run_block(b, block, body);
 }

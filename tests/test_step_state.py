@@ -255,8 +255,8 @@ STEP_CASES = {
     "learned_partition_count": (lambda oracle: _recount_text(11), 31, 1, {}, {}),
     # deferred placement whose placement kernel spills more than the spill list holds (79 K records into regions of one record; the scan places
     # 2/16 of the partitions and spills less than the list's 64 K, k_place the other 14/16).  Whichever check sees the overflow first -- the one
-    # behind the scan (the simulator's k_place has run by then) or the one behind the first count tier, which counts again with deferral off
-    # once (defer_off_once, host_count.h) -- the step ends in the exact layout, and steps 2 and 3 must take the same path
+    # behind the scan (the simulator's k_place has run by then) or the one behind the first count tier, which runs the step again with deferral
+    # off (allow_defer, count_impl in host_count.h) -- the step ends in the exact layout, and steps 2 and 3 must take the same path
     "deferred_spill_overflow": (_synth(560, 150, 3), 11, 2, dict(log2_partitions=10),
                                 {"CDBG_SCAN_MODE": "capped", "CDBG_DEFER_SLICES": "2,14", "CDBG_PART_CAP": "1"}),
     "var_overflow_regions": (_synth(1500, 150, 3 | 0x100), 31, 2, dict(log2_partitions=6), {"CDBG_SCAN_MODE": "var", "CDBG_PART_CAP": "8"}),
