@@ -88,14 +88,22 @@ struct CompactParams {
 // join buckets of the glue stage: <= JB_CAP records each, chosen by a hash of the junction key; a record = W key words
 // + the tag word, ONE scattered store
 constexpr uint32_t JB_CAP = 256;
+// The put in two halves: the place of a record depends on its junction key alone, so a caller that knows the key before it knows
+// the tag (k_compact_wave.h) takes the place early -- the returning device atomic -- and stores when the tag is known.
 template <int W>
-CDBG_DEV void join_bucket_put(uint32_t* jfill, uint64_t* jrecs, int log_jb, uint32_t* error, const Kmer<W>& jc, uint32_t tag) {
-    const uint32_t b = log_jb ? jc.hash_lds() >> (32 - log_jb) : 0u;
-    const uint32_t pos = atomic_add_u32(&jfill[b], 1u);
+CDBG_DEV uint32_t join_bucket_of(int log_jb, const Kmer<W>& jc) { return log_jb ? jc.hash_lds() >> (32 - log_jb) : 0u; }
+template <int W>
+CDBG_DEV uint32_t join_bucket_reserve(uint32_t* jfill, int log_jb, const Kmer<W>& jc) { return atomic_add_u32(&jfill[join_bucket_of<W>(log_jb, jc)], 1u); }
+template <int W>
+CDBG_DEV void join_bucket_store(uint64_t* jrecs, int log_jb, uint32_t* error, const Kmer<W>& jc, uint32_t pos, uint32_t tag) {
     if (pos >= JB_CAP) { *error = 8; return; }           // (the host falls back: log + global table)
-    const uint64_t o = (uint64_t)b * JB_CAP + pos;
+    const uint64_t o = (uint64_t)join_bucket_of<W>(log_jb, jc) * JB_CAP + pos;
     if (W == 1) { uint4 r; r.x = (uint32_t)jc.w[0]; r.y = (uint32_t)(jc.w[0] >> 32); r.z = tag; r.w = 0; reinterpret_cast<uint4*>(jrecs)[o] = r; }
     else { for (int j = 0; j < W; ++j) jrecs[o * (W + 1) + j] = jc.w[j]; jrecs[o * (W + 1) + W] = tag; }
+}
+template <int W>
+CDBG_DEV void join_bucket_put(uint32_t* jfill, uint64_t* jrecs, int log_jb, uint32_t* error, const Kmer<W>& jc, uint32_t tag) {
+    join_bucket_store<W>(jrecs, log_jb, error, jc, join_bucket_reserve<W>(jfill, log_jb, jc), tag);
 }
 // one glue record: into its join bucket, or at position o of the sequential log
 template <int W>

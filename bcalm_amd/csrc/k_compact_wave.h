@@ -14,6 +14,21 @@
 // workgroup tiers of k_compact.h still probe for successors) -- 9 KB of LDS per wave for one-word k-mers.
 // Buckets with more entries than TSW/2 (or more junctions than the table takes) are deferred: to a second launch of
 // this kernel with a table twice the size (W >= 2), then to the workgroup-per-bucket tiers of k_compact.
+//
+// Glue records.  The ends that post one -- open ends of home k-mers, and CONFIRMs between two travellers -- go on ONE compact
+// list (ballot + popcount over a wave-uniform cursor, in the pass that lists the terminals; the list lives in the half of the
+// junction table's memory that the terminal list leaves free, so the LDS did not grow).  A bucket at sequencing depth has 31 - 37
+// of them among its ~310 ends: one 64-lane step.  Before, two passes walked all ends in 5 steps each with ~12 % of the lanes at
+// work, and every step ended in an LDS atomic, the junction + hash code and a RETURNING device atomic on the join bucket's fill
+// word with a 16-byte store waiting for it: ~5 exposed round trips to a memory-side atomic per bucket.  Now the first 64 list
+// entries take their places in one step behind walk 2 (CwHold), the round trip passes behind the base output, and the records
+// are stored at the end of the bucket; the list index is the record's place in the sequential log (no LDS atomic on that path).
+// The last-base pass between the two no longer indexes the literal "ACGT": that was a global load and an s_waitcnt vmcnt(0) in
+// every step, which also cut short whatever was in flight.
+// Tried and dropped (compiler's resource usage, gfx950, no GPU needed): two held steps, and the reservation before walk 2 as first
+// planned -- either puts k_compact_wave<1, 512> into scratch memory (walk 2 is the kernel's register peak); a held step for k-mers
+// of two, three or seven words (scratch, or a wave per SIMD less: CwHold).  Not attempted: positions without the second chain walk.
+// Times before / after: profiles/README.md, round 7.
 #pragma once
 #include "k_compact.h"
 
@@ -34,13 +49,20 @@ struct CompactWaveLds {                                 // one per wave
     static_assert(TSW <= 512 || W <= 4, "the 1024-slot wave tier: k <= 127 (16-bit base offsets: EMAX * k = 512 * 127 < 65536)");
     uint64_t ekeys[EMAX * W];                           // the bucket's k-mers in entry order: word i of entry e at [i * EMAX + e]
     uint32_t jt[TSW];                                   // junction table: one slot per junction that an end of the bucket registers at (cw_jt_*);
-                                                        // once the links are known, its memory holds the terminal ends of home entries (walk 1 work list)
+                                                        // once the links are known, its memory holds two lists of 16-bit end ids: in the lower half the
+                                                        // terminal ends of home entries (walk 1 work list), in the upper half the ends that post a glue
+                                                        // record (kept to the end of the bucket)
     uint32_t cnt[EMAX];                                 // count | TRAV_FLAG; after walk 2: (byte offset << 1) | strand
     uint16_t lnk[2 * EMAX];                             // per end (2 * entry + end): note, then link word
     uint16_t pdesc[EMAX], pn[EMAX], pb[EMAX];           // pieces: start end (bit 15: cyclic), k-mers, relative base offset
     uint8_t vis[EMAX];                                  // bit 0 visited, bit 1 traveller, bit 2 / 3 owns the junction at the left / right end
-    uint32_t np, nb, nb2, nopen, nconf, lw, ncyc, pad, ncov;   // pad: number of terminals
+    uint32_t np, nb, nb2, ncyc, pad, ncov;              // pad: number of terminals
 };
+// (the LDS decides the waves per CU: a two-wave workgroup of one-word k-mers takes 15.9 of the 16 KB that 20 waves per CU allow.  No
+//  instantiation may grow beyond what it took with the three glue-record counters it had before the record list: 36 bytes of counters)
+template <int W, int TSW> constexpr size_t cw_lds_bytes_before = ((size_t)(TSW / 2) * (8 * W + 15) + (size_t)TSW * 4 + 36 + 7) / 8 * 8;
+static_assert(cw_lds_bytes_before<1, 512> == 7976 && sizeof(CompactWaveLds<1, 512>) <= 7976, "k_compact_wave<1, 512>: 20 waves per CU");
+// (every other instantiation: checked where the kernel declares its LDS)
 
 template <int W, int TSW>
 CDBG_DEV Kmer<W> cw_key(const CompactWaveLds<W, TSW>& L, uint32_t e) {
@@ -156,6 +178,23 @@ CDBG_DEV void cw_load_entries(const CompactParams& P, uint64_t so, uint32_t E, i
         }
     }
 }
+// rank of this lane among the set bits of a ballot
+#ifdef CDBG_HOSTSIM
+CDBG_DEV uint32_t cw_rank_in(uint64_t m, int lane) { return (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL)); }
+#else
+CDBG_DEV uint32_t cw_rank_in(uint64_t m, int) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+#endif
+// tag of the glue record of an end on the record list, from the end's final link word: POSTED by walk 2 -- an open piece end, the piece's
+// id and side (tag0: twice the id of the bucket's first piece) plus its own confirmation -- or a CONFIRM alone
+CDBG_DEV uint32_t cw_glue_tag(uint32_t l, uint32_t tag0) {
+    return (l & CWL_POSTED) ? ((tag0 + (l & 0x3FFu)) | ((l & CWL_CONF) ? GTAG_CONFBIT : 0u)) : GTAG_CONFIRM;
+}
+// Steps of 64 glue records whose join-bucket places a wave holds in registers between the reservation and the store: one, where that
+// costs neither scratch memory nor a wave per SIMD (compiler's resource usage, gfx950).  Two steps, or one held across walk 2, send
+// k_compact_wave<1, 512> (96 VGPRs for 5 waves per SIMD) to scratch; k_compact_wave<2, 256> (80 VGPRs for 6) has no register left at
+// all, and <3, 256> / <7, 128> would drop from 5 to 4 / 4 to 3 waves per SIMD.  Held therefore for one- and four-word k-mers (BASELINE
+// configs 3 and 5), checked for every table size; for the others the records reserve and store in one go.
+template <int W, int TSW> struct CwHold { static constexpr int STEPS = (W == 1 || W == 4) ? 1 : 0; };
 // One bucket.  X: its entries (requested one bucket ago); E, so: its segment.
 #if defined(CDBG_PROFILE_PHASES) && !defined(CDBG_HOSTSIM)
 #define CDBG_WPH(i) do { const uint64_t t_ = clock64(); acc[4 + (i)] += t_ - acc[15]; acc[15] = t_; } while (0)
@@ -169,7 +208,7 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
     constexpr int NPER = CwEntries<W, TSW>::NPER;
     const int k = P.k;
     const uint32_t pg = (p << P.rank_bits) | (uint32_t)P.rank;
-    if (lane == 0) { L.np = 0; L.nb = 0; L.nb2 = 0; L.nopen = 0; L.nconf = 0; L.lw = 0; L.ncyc = 0; L.pad = 0; L.ncov = 0; }
+    if (lane == 0) { L.np = 0; L.nb = 0; L.nb2 = 0; L.ncyc = 0; L.pad = 0; L.ncov = 0; }
 
     // ---- load the bucket: home + traveller solid k-mers (the table is empty: the previous bucket emptied its slots) ----
     uint32_t n_home = 0;
@@ -243,7 +282,7 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
                 else {
                     // 1-1 junction with a traveller on at least one side: confirm it for glue, once (a home end is open and
                     // posted anyway: its confirmation rides on that record)
-                    if (home || (!yhome && e < y)) { conf = true; if (!home) atomic_add_u32(&L.nconf, 1u); }
+                    if (home || (!yhome && e < y)) conf = true;
                     if (home) link = LNK_OPEN;
                 }
             }
@@ -252,13 +291,29 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
     }
     CDBG_WAVE_SYNC();
     // terminal ends of home entries: the walk-1 work list, in the memory of the junction table (dead from here on: 1 KB per wave
-    // less is a fifth more waves per CU for one-word k-mers)
+    // less is a fifth more waves per CU for one-word k-mers).
+    // The ends that will post a glue record -- an open end of a home k-mer (walk 2 marks it POSTED), or a CONFIRM that no open home
+    // end carries (both k-mers travellers) -- go on a second list in the upper half of that memory, in end order: lanes of one step
+    // take consecutive places from a ballot over a wave-uniform cursor (every lane runs every step).  Its length is the bucket's
+    // glue-record count, and a record's index in it is its place in the sequential log.
     uint16_t* const term = reinterpret_cast<uint16_t*>(L.jt);
-    for (uint32_t it = lane; it < 2 * E; it += 64) {
-        if (!(L.cnt[it >> 1] & TRAV_FLAG) && (L.lnk[it] & 3u) != LNK_INTERNAL) {
-            const uint32_t ti = atomic_add_u32(&L.pad, 1u);
-            term[ti] = (uint16_t)it;
+    uint16_t* const grec = term + TSW;                   // (at most 2 E <= TSW ends on either list)
+    uint32_t nrec = 0, nconf = 0;
+    for (uint32_t it0 = 0; it0 < 2 * E; it0 += 64) {
+        const uint32_t it = it0 + (uint32_t)lane;
+        bool open = false, conf = false;
+        if (it < 2 * E) {
+            const uint32_t l = L.lnk[it];
+            if (!(L.cnt[it >> 1] & TRAV_FLAG) && (l & 3u) != LNK_INTERNAL) {
+                const uint32_t ti = atomic_add_u32(&L.pad, 1u);
+                term[ti] = (uint16_t)it;
+            }
+            open = (l & 3u) == LNK_OPEN;                 // (home ends only: a traveller's end is DEAD)
+            conf = (l & CWL_CONF) && !open;              // (open home ends carry their confirmation themselves)
         }
+        const uint64_t mrec = __ballot(open || conf), mconf = __ballot(conf);
+        if (open || conf) grec[nrec + cw_rank_in(mrec, lane)] = (uint16_t)it;
+        nrec += (uint32_t)__popcll(mrec); nconf += (uint32_t)__popcll(mconf);
     }
     CDBG_WAVE_SYNC();
 
@@ -279,12 +334,10 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
             L.pdesc[li] = (uint16_t)it; L.pn[li] = (uint16_t)n;
             atomic_add_u32(&L.nb, n + (uint32_t)k - 1u);
             atomic_add_u32(&L.ncov, n);
-            const uint32_t no = ((L.lnk[it] & 3u) == LNK_OPEN ? 1u : 0u) + ((L.lnk[other] & 3u) == LNK_OPEN ? 1u : 0u);
-            if (no) atomic_add_u32(&L.nopen, no);
         }
     }
     CDBG_WAVE_SYNC();
-    for (uint32_t i = lane; i < (uint32_t)TSW; i += 64) L.jt[i] = 0u;   // the work list is consumed: the table goes back empty, for the next bucket
+    for (uint32_t i = lane; i < (uint32_t)TSW / 2; i += 64) L.jt[i] = 0u;   // the work list is consumed: its half of the table goes back empty, for the next bucket
     // ---- closed chains entirely inside the bucket (isolated cycles): only when the linear pieces do not cover every
     // home entry (rare).  Mark what the pieces cover, then cut each remaining cycle at its smallest entry. ----
     if (uni_u32(L.ncov) != n_home) {
@@ -320,25 +373,15 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
     CDBG_WPH(4);
     // ---- output space: piece ids, base bytes, glue-log records from this wave's chunks ----
     uint32_t np = uni_u32(L.np);
-    const uint32_t nb = uni_u32(L.nb), nconf = uni_u32(L.nconf), nlog = nconf + uni_u32(L.nopen);
+    const uint32_t nb = uni_u32(L.nb), nlog = nrec;
     const uint64_t pbase = cw_reserve(pc, P.piece_cursor, np, CW_PIECE_CHUNK, lane);
     const uint64_t bbase = cw_reserve(bc, P.bases_cursor, nb, CW_BASES_CHUNK, lane);
     uint64_t lbase = cw_reserve(lc, P.glog_cursor, nlog, CW_GLOG_CHUNK, lane);
-    bool log_ok = true;
-    if (pbase + np > P.piece_cap || bbase + nb > P.bases_cap) { if (lane == 0) *P.error = 3; np = 0; }
-    if (lbase + nlog > P.glog_cap) { if (lane == 0) *P.error = 5; np = 0; lbase = 0; log_ok = false; }   // never write past the log
+    bool ok = true;                                      // (errors 3 and 5: the bucket writes nothing, the host repeats the stage)
+    if (pbase + np > P.piece_cap || bbase + nb > P.bases_cap) { if (lane == 0) *P.error = 3; np = 0; ok = false; }
+    if (lbase + nlog > P.glog_cap) { if (lane == 0) *P.error = 5; np = 0; lbase = 0; ok = false; }   // never write past the log
 
-    // ---- glue log, part 1: CONFIRM records of junctions whose two k-mers are both travellers here ----
-    if (log_ok && nconf) {
-        for (uint32_t it = lane; it < 2 * E; it += 64) {
-            const uint32_t l = L.lnk[it];
-            if (!(l & CWL_CONF) || (l & 3u) == LNK_OPEN) continue;   // open home ends carry their confirmation themselves
-            const uint64_t o = lbase + atomic_add_u32(&L.lw, 1u);
-            const Kmer<W> jc = canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k);
-            glue_record_put<W>(P, o, jc, GTAG_CONFIRM);
-        }
-    }
-    CDBG_WAVE_SYNC();                                    // walk 2 rewrites the link words this pass reads
+    CDBG_WAVE_SYNC();
     CDBG_WPH(5);
     // ---- walk 2: one lane per piece hands every k-mer its byte offset + strand (stored over the k-mer's count, which
     // is summed here), marks the open ends and writes the piece's first k-1 bases ----
@@ -375,6 +418,32 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
         }
     }
     CDBG_WAVE_SYNC();
+    // ---- glue records, part 1: their places in the join buckets.  A place depends on the junction key alone, so the returning
+    // device atomic is issued here -- one step of 64 list entries -- and its round trip passes behind the base output below; the
+    // place stays in a register until the record is stored at the end of the bucket (one-word k-mers keep the key as well; longer
+    // ones form it again, for the registers).  Not earlier: walk 2 is where this kernel needs the most registers, a value held across
+    // it goes to scratch memory.  The records beyond the held step reserve and store in one go, at the end.
+    // (A place reserved by a bucket that then fails -- error 8 here or in any other bucket -- stays empty: harmless, because jfill
+    //  and the records of an attempt are never read after an error.  host_compact.h zeroes jfill at the start of EVERY attempt of
+    //  its retry loop, before the first tier, and leaves direct mode for good on an error 8 that larger buckets cannot cure; the glue stage zeroes it again
+    //  before a scatter of its own, host_glue.h / host_glue_sharded.h.)
+    constexpr int HOLD = CwHold<W, TSW>::STEPS;
+    const bool direct = P.jrecs != nullptr;
+    uint32_t hpos[HOLD + 1]; uint64_t hkey[HOLD + 1];
+#pragma unroll
+    for (int s = 0; s <= HOLD; ++s) { hpos[s] = 0; hkey[s] = 0; }
+    if (ok && direct) {
+#pragma unroll
+        for (int s = 0; s < HOLD; ++s) {
+            const uint32_t j = 64u * (uint32_t)s + (uint32_t)lane;
+            if (j < nrec) {
+                const uint32_t it = grec[j];
+                const Kmer<W> jc = canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k);
+                hpos[s] = join_bucket_reserve<W>(P.jfill, P.log_jb, jc);
+                if (W == 1) hkey[s] = jc.w[0];
+            }
+        }
+    }
     // the first k-1 bases of every piece -- the start k-mer, read leaving through the far end of the start terminal -- one lane
     // per 8 bases (an unaligned 8-byte store; the last chunk of a piece overlaps the one before): with one lane per piece the
     // 16 stores of a 127-mer's prefix were serial work of a few lanes (walk 2: a third of this kernel at k = 127)
@@ -398,24 +467,57 @@ CDBG_DEV void compact_bucket_wave(const CompactParams& P, CompactWaveLds<W, TSW>
             const uint32_t v = L.cnt[e];
             const Kmer<W> x = cw_key<W, TSW>(L, e);
             const uint32_t b = (v & 1u) ? 3u - x.base(k, 0) : x.base(k, k - 1);
-            out[v >> 1] = (uint8_t)("ACGT"[b]);
+            out[v >> 1] = (uint8_t)(0x54474341u >> (8u * b));   // "ACGT"[b] by arithmetic: indexing the literal is a global load and a wait for it in every step
         }
-        // ---- glue log, part 2: one record per open piece end ----
-        for (uint32_t it = lane; it < 2 * E; it += 64) {
-            const uint32_t l = L.lnk[it];
-            if (!(l & CWL_POSTED)) continue;
-            const uint64_t o = lbase + atomic_add_u32(&L.lw, 1u);
-            const Kmer<W> jc = canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k);
-            glue_record_put<W>(P, o, jc, (uint32_t)(pbase * 2 + (l & 0x3FFu)) | ((l & CWL_CONF) ? GTAG_CONFBIT : 0u));
+    }
+    // ---- glue records, part 2: one per list entry, tagged from the link word that walk 2 left at its end ----
+    if (ok && nrec) {
+        const uint32_t tag0 = (uint32_t)(pbase * 2);
+        if (direct) {
+#pragma unroll
+            for (int s = 0; s < HOLD; ++s) {
+                const uint32_t j = 64u * (uint32_t)s + (uint32_t)lane;
+                if (j < nrec) {
+                    const uint32_t it = grec[j], l = L.lnk[it];
+                    const uint32_t tag = cw_glue_tag(l, tag0);
+                    Kmer<W> jc;
+                    if (W == 1) jc.w[0] = hkey[s]; else jc = canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k);
+                    join_bucket_store<W>(P.jrecs, P.log_jb, P.error, jc, hpos[s], tag);
+                }
+            }
+            for (uint32_t j = 64u * HOLD + (uint32_t)lane; j < nrec; j += 64) {   // (more records than the registers hold)
+                const uint32_t it = grec[j], l = L.lnk[it];
+                const uint32_t tag = cw_glue_tag(l, tag0);
+                join_bucket_put<W>(P.jfill, P.jrecs, P.log_jb, P.error, canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k), tag);
+            }
+        } else {
+            // the sequential log (several ranks, CDBG_GLUE_TABLE, CDBG_GLUE_LOG): the list index is the record's place
+            for (uint32_t j = lane; j < nrec; j += 64) {
+                const uint32_t it = grec[j], l = L.lnk[it];
+                const uint32_t tag = cw_glue_tag(l, tag0);
+                const Kmer<W> jc = canon_junction_at<W>(cw_key<W, TSW>(L, it >> 1), it & 1u, k);
+                const uint64_t o = lbase + j;
+                for (int i = 0; i < W; ++i) P.glog_keys[o * W + i] = jc.w[i];
+                P.glog_tag[o] = tag;
+            }
         }
     }
     CDBG_WAVE_SYNC();
+    for (uint32_t i = (uint32_t)TSW / 2 + lane; i < (uint32_t)TSW; i += 64) L.jt[i] = 0u;   // the record list is consumed: the table's other half goes back empty
 #ifdef CDBG_WAVE_DEBUG
     if (lane == 0) { for (uint32_t it = 0; it < 2 * E; ++it) fprintf(stderr, " [%u cnt %x vis %x lnk %04x]", it, L.cnt[it >> 1], L.vis[it >> 1], L.lnk[it]); fprintf(stderr, "\n"); }
-    if (lane == 0) fprintf(stderr, "bucket %u E %u np %u nconf %u nopen %u lw %u pbase %llu lbase %llu nterm %u ncov %u nhome %u\n", p, E, np, nconf, L.nopen, L.lw, (unsigned long long)pbase, (unsigned long long)lbase, nterm, L.ncov, n_home);
+    if (lane == 0) fprintf(stderr, "bucket %u E %u np %u nconf %u nopen %u lw %u pbase %llu lbase %llu nterm %u ncov %u nhome %u\n", p, E, np, nconf, nrec - nconf, nrec, (unsigned long long)pbase, (unsigned long long)lbase, nterm, L.ncov, n_home);
 #endif
-    const uint32_t nopen_posted = np ? uni_u32(L.lw) - (log_ok ? nconf : 0u) : 0u;
-    acc[0] += nopen_posted; acc[1] += log_ok ? nconf : 0u; acc[2] += uni_u32(L.ncyc); acc[3] += np;
+#ifdef CDBG_HOSTSIM
+    // (the simulator build, for the tests of the record batching: CDBG_SIM_CW_TRACE=<file> gets one line per bucket -- table size, bucket,
+    //  entries, glue records, the CONFIRMs among them, pieces, then the k-mers of every piece)
+    if (lane == 0) if (const char* tf = getenv("CDBG_SIM_CW_TRACE")) if (FILE* fp = fopen(tf, "a")) {
+        fprintf(fp, "%d %u %u %u %u %u", TSW, p, E, nrec, nconf, np);
+        for (uint32_t li = 0; li < np; ++li) fprintf(fp, " %u", (unsigned)L.pn[li]);
+        fprintf(fp, "\n"); fclose(fp);
+    }
+#endif
+    acc[0] += ok ? nrec - nconf : 0u; acc[1] += ok ? nconf : 0u; acc[2] += uni_u32(L.ncyc); acc[3] += np;
     CDBG_WPH(7);
     CDBG_WAVE_SYNC();
     CDBG_WPH(8);
@@ -443,6 +545,7 @@ template <int W, int TSW>
 #define CDBG_CW_WAVES4 3
 #endif
 __global__ void __launch_bounds__(CW_THREADS, W == 1 ? (TSW > 512 ? 3 : CDBG_CW_WAVES1) : W == 2 ? (TSW > 256 ? 2 : CDBG_CW_WAVES2) : (TSW > 256 ? 2 : CDBG_CW_WAVES4)) k_compact_wave(CompactWaveParams WP) {
+    static_assert(sizeof(CompactWaveLds<W, TSW>) <= cw_lds_bytes_before<W, TSW>, "the wave tiers' LDS must not grow");
     CDBG_SHARED CompactWaveLds<W, TSW> Ls[CW_THREADS / 64];
     const CompactParams& P = WP.c;
     const int tid = threadIdx.x, lane = tid & 63, wave = (int)uni_u32((uint32_t)tid >> 6);
