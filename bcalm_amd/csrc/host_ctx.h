@@ -149,7 +149,8 @@ constexpr int TS_COUNT_1 = CDBG_TSC1, TS_COUNT_2 = CDBG_TSC2, TS_COUNT_4 = CDBG_
 constexpr int TS_COMPACT_1 = CDBG_TSK1, TS_COMPACT_2 = 512, TS_COMPACT_4 = 512;
 // k-mers wider than four words (k = 128 .. 255: the reference's KSIZE_LIST is open-ended, README.md:91-99 -- "must contain 32", larger
 // spans are a build option there as here: CDBG_MAX_W).  Same kernels, tables a quarter / half the slots of the four-word geometry so that
-// keys of 40 - 64 bytes still fit the CU's LDS; not tuned (no BASELINE config lives there), parity-tested at k = 128, 191 and 255.
+// keys of 40 - 64 bytes still fit the CU's LDS; not tuned (no BASELINE config lives there); tested against the oracle at k = 32 (W - 1), + 1, + 15, + 16, 32 W - 2 and 32 W - 1 of every W, with one
+// partition per W pushed through every count and compaction tier (tests/kwidth_cases.py: simulator and device).
 #ifndef CDBG_MAX_W
 #define CDBG_MAX_W 8
 #endif

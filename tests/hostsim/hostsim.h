@@ -143,7 +143,7 @@ inline void run_block(unsigned bx, unsigned nthreads, const std::function<void()
 template <class F>
 inline void launch(unsigned grid, unsigned block, F f) {
     std::function<void()> body = f;
-    // CDBG_SIM_TRACE=<file> (dev aid, no test depends on it): one line per launch -- kernel text, grid, block -- appended to that file;
+    // CDBG_SIM_TRACE=<file> (dev aid; tests/test_hostsim_kwidth.py reads the kernel texts, so a renamed template argument shows there): one line per launch -- kernel text, grid, block -- appended to that file;
     // "%p" in the name becomes the process id (one file per rank of a multi-process test)
     if (const char* e = getenv("CDBG_SIM_TRACE")) if (*e) {
         std::string name(e);
