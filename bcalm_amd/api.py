@@ -48,7 +48,7 @@ EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
-           "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs",
+           "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -112,6 +112,9 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_fetch_links.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.cdbg_unitig_id_base.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     lib.cdbg_load_unitigs.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
+    lib.cdbg_index.argtypes = [vp]
+    lib.cdbg_index_info.argtypes = [vp, C.POINTER(u64)]
+    lib.cdbg_query.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -210,6 +213,48 @@ class Graph:
                 raise ValueError("kc: one value per sequence")
             kcs = (C.c_uint64 * max(len(bs), 1))(*[int(x) for x in kc])
         self._ck(self.lib.cdbg_load_unitigs(self._h, b"".join(bytes(b) for b in bs), off, len(bs), kcs))
+
+    # ---- node lookup (cdbg_index / cdbg_query) ----
+    MISS = 0xFFFFFFFFFFFFFFFF
+
+    def index(self):
+        """build the k-mer index of the resident unitig set (after run() / glue() / load_unitigs()); a no-op when it is there"""
+        self._ck(self.lib.cdbg_index(self._h))
+
+    def index_info(self) -> dict:
+        """{positions, distinct, slots, bytes} of the index (built when it is not there)"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.cdbg_index_info(self._h, out))
+        return {"positions": out[0], "distinct": out[1], "slots": out[2], "bytes": out[3]}
+
+    def query_raw(self, seqs, first_offset=0):
+        """-> (hits, offsets): one 64-bit hit word per base of the concatenated sequences (include/cdbg.h cdbg_query: MISS, or
+        unitig << 33 | offset << 1 | strand) as a ctypes array, and the offsets[n + 1] of the sequences in it -- no Python object per
+        k-mer.  first_offset: the sequences start that many bytes into the buffer handed to the library (offsets[0] != 0)"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = first_offset
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        hits = (C.c_uint64 * max(acc - first_offset, 1))()
+        self._ck(self.lib.cdbg_query(self._h, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), hits))
+        return hits, [o - first_offset for o in off]
+
+    def query(self, seqs):
+        """-> per sequence the list of its len - k + 1 k-mers' places (empty when shorter than k): None, or (unitig, offset, strand)
+        with unitig = the position in unitigs(), offset = the k-mer's first base there, strand "+" (the unitig reads as the k-mer)
+        or "-" (as its reverse complement)"""
+        hits, off = self.query_raw(seqs)
+        out = []
+        for i in range(len(off) - 1):
+            row = []
+            for p in range(off[i], max(off[i], off[i + 1] - self.k + 1)):
+                h = hits[p]
+                row.append(None if h == self.MISS else (h >> 33, (h >> 1) & 0xFFFFFFFF, "-" if h & 1 else "+"))
+            out.append(row)
+        return out
 
     def generate_reads(self, n_reads, read_len, cfg, first_read=0, total_reads=None):
         total = n_reads if total_reads is None else total_reads

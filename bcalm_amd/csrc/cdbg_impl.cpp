@@ -37,6 +37,7 @@
 #include "k_count_fast.h"
 #include "k_compact_wave.h"
 #include "k_split.h"
+#include "k_index.h"
 
 using namespace cdbg;
 
@@ -47,6 +48,7 @@ using namespace cdbg;
 #include "host_glue_sharded.h"
 #include "host_glue.h"
 #include "host_relink.h"
+#include "host_index.h"
 
 
 // =======================================================================================
@@ -228,7 +230,7 @@ int cdbg_count(cdbg_ctx* c) {
     return CDBG_OK;
 }
 int cdbg_compact(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); CK(refuse_loaded(c, "cdbg_compact")); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(compact_impl) }
-int cdbg_glue(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); CK(refuse_loaded(c, "cdbg_glue")); (void)hipSetDevice(c->prm.device_id); DISPATCH_W(glue_impl) }
+int cdbg_glue(cdbg_ctx* c) { if (!c) return fail(CDBG_E_PARAM, "null context"); CK(refuse_loaded(c, "cdbg_glue")); (void)hipSetDevice(c->prm.device_id); index_forget(c); DISPATCH_W(glue_impl) }
 int cdbg_run(cdbg_ctx* c) { CK(refuse_loaded(c, "cdbg_run")); CK(cdbg_count(c)); CK(cdbg_compact(c)); return cdbg_glue(c); }
 static int relink_dispatch(cdbg_ctx* c) { DISPATCH_W(relink_impl) }
 int cdbg_link(cdbg_ctx* c) {
@@ -240,7 +242,26 @@ int cdbg_link(cdbg_ctx* c) {
 int cdbg_load_unitigs(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_unitigs, const uint64_t* kc) {
     if (!c || !offsets || (!bases && n_unitigs)) return fail(CDBG_E_PARAM, "null argument");
     (void)hipSetDevice(c->prm.device_id);
+    index_forget(c);
     return load_unitigs_impl(c, bases, offsets, n_unitigs, kc);
+}
+// ---- node lookup (k_index.h, host_index.h) ----
+int cdbg_index(cdbg_ctx* c) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(index_impl, c, "cdbg_index") } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_index: out of host memory"); }
+}
+int cdbg_index_info(cdbg_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { CK(cdbg_index(c)); } catch (...) { return fail(CDBG_E_INTERNAL, "cdbg_index_info"); }
+    for (int i = 0; i < 4; ++i) out[i] = c->index_info[i];
+    return CDBG_OK;
+}
+int cdbg_query(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t* hits) {
+    if (!c || (n_seqs && (!offsets || !bases || !hits))) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(query_impl, c, bases, offsets, n_seqs, hits) } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_query: out of host memory"); }
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");
@@ -267,6 +288,7 @@ int cdbg_reset(cdbg_ctx* c) {
     prewarm_join(c);
     if (c->place_stream) (void)hipStreamSynchronize(c->place_stream);   // (a count stage that returned with an error may have left its placement stream busy)
     c->stage = 0; c->loaded = false; c->st = cdbg_stats_t{};
+    index_forget(c);                                 // (the table goes back to the pool)
     c->n_solid_entries = c->n_pieces = c->n_piece_bases = c->n_unitigs = c->unitig_total = 0; c->linked = false; c->n_links = 0; c->joined = false;
     c->xchg_done = false; c->xp_ab_ready = false; c->comm_bytes = 0; c->piece_lo = c->piece_hi = 0; c->ss_on = false; c->expect_bytes = 0;
     return CDBG_OK;                                  // reads and every device buffer stay resident

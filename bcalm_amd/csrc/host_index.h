@@ -1,0 +1,136 @@
+// host_index.h -- libcdbg.so, host side of cdbg_index / cdbg_index_info / cdbg_query (k_index.h): the position table over the resident
+// unitig set, and the batched lookup of a caller's sequences in it.  Included by cdbg_impl.cpp only.
+#pragma once
+
+namespace {
+
+// whatever replaces the resident set forgets its index: the table goes back to the pool
+void index_forget(cdbg_ctx* c) {
+    c->indexed = false; c->index_slots.release();
+    for (uint64_t& v : c->index_info) v = 0;
+}
+
+int index_refuse(const cdbg_ctx* c, const char* what) {
+    if (c->prm.world_size != 1 || c->force_multi || c->knobs.get("CDBG_FORCE_MULTI"))
+        return fail(CDBG_E_STATE, "%s: one rank only (world_size == 1): a rank that holds a share of the unitigs cannot answer for the graph", what);
+    if (c->stage < 3) return fail(CDBG_E_STATE, "%s before cdbg_glue", what);
+    return CDBG_OK;
+}
+
+template <int W>
+int index_impl(cdbg_ctx* c, const char* what) {
+    CK(index_refuse(c, what));
+    if (c->indexed) return CDBG_OK;
+    hipStream_t s = c->stream;
+    const uint64_t U = c->n_unitigs;
+    DBuf<uint32_t> kcount; DBuf<uint64_t> kmer_off, out;
+    CK(kcount.alloc(U, false)); CK(kmer_off.alloc(U + 1, false)); CK(out.alloc(4, false));
+    IndexParams ip{};
+    ip.n_unitigs = U; ip.k = c->k; ip.unitig_off = c->unitig_off.p; ip.unitig_len = c->unitig_len.p; ip.packed = c->unitig_packed.p;
+    ip.kcount = kcount.p; ip.kmer_off = kmer_off.p; ip.out = out.p;
+    if (U) CDBG_LAUNCH(k_index_lens, (U + INDEX_THREADS - 1) / INDEX_THREADS, INDEX_THREADS, s, ip);
+    CK(exscan_u32(c, kcount.p, kmer_off.p, U));
+    uint64_t P = 0; CK(read_u64(kmer_off.p + U, &P));
+    ip.n_pos = P;
+    // slots: the smallest power of two >= 1.5 P + 64.  CDBG_INDEX_LOG2_SLOTS (test hook): a second build into a smaller table, never
+    // below the smallest power of two > distinct k-mers -- the first build counted them -- so that one slot at least stays empty
+    uint64_t slots = pow2_at_least(P + P / 2 + 64), o[3] = { 0, 0, 0 };
+    for (int pass = 0; pass < 2; ++pass) {
+        if (const int rc = c->index_slots.alloc(slots, false)) {
+            if (rc != CDBG_E_NOMEM) return rc;
+            const std::string why = g_err;
+            return fail(CDBG_E_NOMEM, "cdbg_index: a table of %llu slots (%llu bytes) for %llu k-mer positions does not fit: %s",
+                        (unsigned long long)slots, (unsigned long long)(slots * sizeof(uint64_t)), (unsigned long long)P, why.c_str());
+        }
+        HIPCK(hipMemsetAsync(c->index_slots.p, 0xFF, slots * sizeof(uint64_t), s));   // (pool blocks come back dirty: on every build)
+        HIPCK(hipMemsetAsync(out.p, 0, 4 * sizeof(uint64_t), s));
+        ip.slots = c->index_slots.p; ip.mask = slots - 1;
+        if (P) {
+            const uint64_t lanes = (P + INDEX_RUN - 1) / INDEX_RUN;
+            CDBG_LAUNCH((k_index_insert<W>), std::min<uint64_t>((lanes + INDEX_THREADS - 1) / INDEX_THREADS, MAX_GRID), INDEX_THREADS, s, ip);
+        }
+        HIPCK(hipStreamSynchronize(s));
+        HIPCK(hipGetLastError());
+        CK(read_u64(out.p, o, 3));
+        if (o[2] || o[0] != P) return fail(CDBG_E_INTERNAL, "cdbg_index: %llu of %llu k-mer positions inserted, %llu found no slot (%llu slots)",
+                                           (unsigned long long)o[0], (unsigned long long)P, (unsigned long long)o[2], (unsigned long long)slots);
+        const char* e = pass == 0 ? c->knobs.get("CDBG_INDEX_LOG2_SLOTS") : nullptr;
+        if (!e) break;
+        const uint64_t want = std::max<uint64_t>(pow2_at_least(o[1] + 1), 1ull << std::min<uint64_t>(strtoull(e, nullptr, 10), 62));
+        if (want >= slots) break;
+        slots = want;
+    }
+    c->index_info[0] = P; c->index_info[1] = o[1]; c->index_info[2] = slots; c->index_info[3] = slots * sizeof(uint64_t);
+    c->indexed = true;
+    return CDBG_OK;
+}
+
+template <int W>
+int query_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64_t n, uint64_t* hits) {
+    CK(index_refuse(c, "cdbg_query"));
+    if (!n) return CDBG_OK;
+    for (uint64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return fail(CDBG_E_PARAM, "cdbg_query: offsets not monotone at sequence %llu", (unsigned long long)i);
+    const uint64_t base0 = off[0], total = off[n] - base0;
+    if (!total) return CDBG_OK;
+    CK(index_impl<W>(c, "cdbg_query"));
+    const uint64_t k = (uint64_t)c->k;
+    // bases per device batch (text + sequence ends + 8 bytes of hits per base); consecutive batches overlap by k - 1 bases
+    uint64_t B = 64ull << 20;
+    if (const char* e = c->knobs.get("CDBG_QUERY_BATCH")) B = strtoull(e, nullptr, 10);
+    B = std::min<uint64_t>(std::max<uint64_t>(B, std::max<uint64_t>(4 * k, 256)), 1ull << 31);
+    CK(ingest_init(c));                                      // the pinned staging pair and its copy stream
+    hipStream_t s = c->stream;
+    std::vector<uint32_t> bnd;
+    const bool marks = HostMarks::enabled();
+    float ms_kernels = 0;
+#ifdef CDBG_PROFILE_PHASES
+    CK(c->q_prof.alloc(2, true));
+#else
+    CK(c->q_prof.alloc(2, false));
+#endif
+    for (uint64_t b0 = 0; b0 < total;) {
+        const uint64_t b1 = std::min(total, b0 + B), nb = b1 - b0;
+        const uint64_t n_out = b1 == total ? nb : nb - (k - 1);
+        CK(c->q_text.alloc(nb, false)); CK(c->q_hits.alloc(n_out, false));
+        int pb = 0; bool busy[2] = { false, false };
+        for (uint64_t d = 0; d < nb; d += cdbg_ctx::STAGE_BYTES, pb ^= 1) {
+            const uint64_t m = std::min<uint64_t>(cdbg_ctx::STAGE_BYTES, nb - d);
+            if (busy[pb]) HIPCK(hipEventSynchronize(c->pin_ev[pb]));
+            memcpy(c->pin[pb], bases + base0 + b0 + d, m);
+            HIPCK(hipMemcpyAsync(c->q_text.p + d, c->pin[pb], m, hipMemcpyHostToDevice, c->copy_stream));
+            HIPCK(hipEventRecord(c->pin_ev[pb], c->copy_stream));
+            busy[pb] = true;
+        }
+        // the sequence ends inside the batch, in its own coordinates (a run of empty sequences is one end), closed by the batch's end
+        bnd.clear();
+        for (const uint64_t* it = std::upper_bound(off, off + n + 1, base0 + b0); it < off + n + 1 && *it < base0 + b1; ++it) {
+            const uint32_t v = (uint32_t)(*it - base0 - b0);
+            if (bnd.empty() || bnd.back() != v) bnd.push_back(v);
+        }
+        bnd.push_back((uint32_t)nb);
+        CK(c->q_bnd.alloc(bnd.size(), false));
+        HIPCK(hipMemcpy(c->q_bnd.p, bnd.data(), bnd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIPCK(hipStreamSynchronize(c->copy_stream));
+        QueryParams qp{};
+        qp.text = c->q_text.p; qp.n_text = nb; qp.n_out = n_out; qp.bnd = c->q_bnd.p; qp.n_bnd = (uint32_t)bnd.size(); qp.k = c->k;
+        qp.packed = c->unitig_packed.p; qp.unitig_off = c->unitig_off.p; qp.slots = c->index_slots.p; qp.mask = c->index_info[2] - 1;
+        qp.hits = c->q_hits.p; qp.out = c->q_prof.p;
+        Timer t; if (marks) CK(t.start(s));
+        CDBG_LAUNCH((k_query<W>), (n_out + QUERY_TILE - 1) / QUERY_TILE, QUERY_THREADS, s, qp);
+        if (marks) { float ms = 0; CK(t.stop(&ms)); ms_kernels += ms; }
+        HIPCK(hipStreamSynchronize(s));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpy(hits + b0, c->q_hits.p, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        b0 += n_out;
+    }
+    if (marks) {                                             // dev aid (CDBG_HOST_MARKS=1; bench_micro/query_timing.py reads it)
+        uint64_t pr[2] = { 0, 0 };
+#ifdef CDBG_PROFILE_PHASES
+        CK(read_u64(c->q_prof.p, pr, 2));
+#endif
+        fprintf(stderr, "[query] positions %llu kernel_ms %.3f looked_up %llu slots_read %llu\n", (unsigned long long)total, ms_kernels, (unsigned long long)pr[0], (unsigned long long)pr[1]);
+    }
+    return CDBG_OK;
+}
+
+}  // namespace

@@ -10,6 +10,9 @@
 //   ./bcalm -in <prefix>.h5 -kmer-size 31 -skip-bcalm -skip-bglue -redo-links [-gfa]
 //     scripts/pufferize.py:61,143 and split_unitigs.py: their pieces carry no links; this mode reads <prefix>.unitigs.fa,
 //     recomputes the L: tokens of its records (cdbg_load_unitigs + cdbg_link) and rewrites the file in place.
+//   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -query queries.fa[.gz] [-out prefix]
+//     reads <prefix>.unitigs.fa, looks every k-mer of the query sequences up in it (cdbg_load_unitigs + cdbg_index + cdbg_query) and
+//     writes <prefix>.query.tsv: name, k-mers, k-mers found, runs qpos:len:unitig:strand:upos.
 // Everything between parsing and writing is three calls into libcdbg.so (include/cdbg.h):
 // this file is the replacement for bcalm_1::execute()/Functor (src/bcalm_1.cpp:49-97).
 #include <zlib.h>
@@ -50,6 +53,7 @@ struct Options {
     bool gfa = false, verbose = false, all_ab = false, no_stream = false;
     bool redo_links = false, skip_bcalm = false, skip_bglue = false;   // -redo-links: only the link step, on an existing <prefix>.unitigs.fa
     std::string solid_out;
+    std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
 
 [[noreturn]] void usage_error(const std::string& msg) { throw std::runtime_error(msg); }
@@ -72,6 +76,7 @@ Options parse(int argc, char** argv) {
         else if (a == "-nb-gpus") o.n_gpus = atoi(need("-nb-gpus"));   // the GPU path's counterpart of -nb-cores: GPUs of this node (power of two)
         else if (a == "-gfa") o.gfa = true;
         else if (a == "-redo-links") o.redo_links = true;             // the reference's hidden option: scripts/pufferize.py:143 tells its users to run it
+        else if (a == "-query") o.query = need("-query");
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -500,12 +505,15 @@ void kept_tokens(const std::string& rest, std::vector<std::string>& out) {
         p = q + 1;
     }
 }
-int redo_links(const Options& o, const std::string& prefix, int threads) {
-    auto t0 = std::chrono::steady_clock::now();
-    const std::string fa = prefix + ".unitigs.fa";
-    auto mp = std::make_shared<Mapped>();
-    { struct stat sb; if (stat(fa.c_str(), &sb) != 0) usage_error("-redo-links: cannot open " + fa + " (the unitigs of an earlier run are expected there)"); }
-    std::vector<FaSlice> slices;
+// the records of a unitigs file in file order -- one arena of bases, offsets, the headers -- as cdbg_load_unitigs takes them (-redo-links and -query)
+struct UnitigFile {
+    std::shared_ptr<Mapped> mp; std::vector<FaSlice> slices;
+    uint64_t nu = 0, tb = 0; std::unique_ptr<char[]> seq; std::vector<uint64_t> off; std::vector<const std::string*> rest;
+};
+void read_unitig_file(const Options& o, const std::string& fa, int threads, const char* mode, UnitigFile& F) {
+    F.mp = std::make_shared<Mapped>();
+    auto& mp = F.mp; auto& slices = F.slices;
+    { struct stat sb; if (stat(fa.c_str(), &sb) != 0) usage_error(std::string(mode) + ": cannot open " + fa + " (the unitigs of an earlier run are expected there)"); }
     if (mp->open(fa)) {                                            // (false: an empty file -- no records)
         const char* p = mp->p; const size_t n = mp->n;
         size_t slice = std::max<size_t>(n / (size_t)(threads * 4) + 1, 8u << 20);
@@ -527,28 +535,40 @@ int redo_links(const Options& o, const std::string& prefix, int threads) {
     // records in file order: one arena, offsets, the headers
     uint64_t nu = 0, tb = 0;
     for (const FaSlice& sl : slices) { nu += sl.recs.size(); tb += sl.bases.size(); }
-    std::unique_ptr<char[]> seq(new char[tb + 1]);
-    std::vector<uint64_t> off(nu + 1, 0); std::vector<const std::string*> rest(nu ? nu : 1, nullptr);
+    F.nu = nu; F.tb = tb;
+    F.seq.reset(new char[tb + 1]);
+    F.off.assign(nu + 1, 0); F.rest.assign(nu ? nu : 1, nullptr);
     {
         uint64_t i = 0, w = 0;
         for (const FaSlice& sl : slices) {
-            if (!sl.bases.empty()) memcpy(seq.get() + w, sl.bases.data(), sl.bases.size());
+            if (!sl.bases.empty()) memcpy(F.seq.get() + w, sl.bases.data(), sl.bases.size());
             for (const FaRecord& r : sl.recs) {
                 if (r.seq_len < (size_t)o.k) usage_error(fa + ": record " + std::to_string(i) + " has " + std::to_string(r.seq_len) + " bases, fewer than k = " + std::to_string(o.k));
-                off[i] = w + r.seq_off; rest[i] = &r.rest; ++i;
+                F.off[i] = w + r.seq_off; F.rest[i] = &r.rest; ++i;
             }
             w += sl.bases.size();
         }
-        off[nu] = tb;
+        F.off[nu] = tb;
     }
+}
+cdbg_ctx* load_unitig_file(const Options& o, const std::string& fa, UnitigFile& F) {
     cdbg_params prm{}; prm.k = o.k; prm.abundance_min = std::max(1, o.amin); prm.minimizer_size = 0; prm.log2_partitions = -1; prm.device_id = o.device; prm.world_size = 1;
     cdbg_ctx* ctx = nullptr; check(cdbg_create(&prm, &ctx));
-    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
-    if (cdbg_load_unitigs(ctx, seq.get(), off.data(), nu, nullptr) != 0) {
+    if (cdbg_load_unitigs(ctx, F.seq.get(), F.off.data(), F.nu, nullptr) != 0) {
         const std::string e = cdbg_last_error(); unsigned long long u = 0;
+        cdbg_destroy(ctx);
         if (sscanf(e.c_str(), "unitig %llu", &u) == 1) usage_error(fa + ": record " + std::to_string(u) + ": " + e);
         usage_error(fa + ": " + e);
     }
+    return ctx;
+}
+int redo_links(const Options& o, const std::string& prefix, int threads) {
+    auto t0 = std::chrono::steady_clock::now();
+    const std::string fa = prefix + ".unitigs.fa";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-redo-links", F);
+    auto& mp = F.mp; const uint64_t nu = F.nu, tb = F.tb; auto& seq = F.seq; auto& off = F.off; auto& rest = F.rest;
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F);
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
     check(cdbg_link(ctx));
     uint64_t nl = 0; check(cdbg_num_links(ctx, &nl));
     std::vector<uint64_t> loff(2 * nu + 1), kc(nu ? nu : 1); std::vector<uint32_t> lto(nl ? nl : 1);
@@ -635,6 +655,136 @@ int redo_links(const Options& o, const std::string& prefix, int threads) {
     return EXIT_SUCCESS;
 }
 
+// ---- -query: which unitig, offset and strand holds every k-mer of the query sequences (cdbg_load_unitigs + cdbg_index + cdbg_query) ----
+// the tolerant serial reader of parse_stream with the record names kept: FASTA / FASTQ, plain or gzip, sequences and qualities may wrap;
+// on_seq(name) is called when a record's sequence is complete and lies at the end of `bases`
+template <class F>
+void parse_queries(const std::string& path, std::string& bases, F&& on_seq) {
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) usage_error("cannot open query file " + path);
+    gzbuffer(f, 1 << 20);
+    std::vector<char> line(1 << 22);
+    int fmt = 0, fq_state = 0; char fq_kind = 0; uint64_t fq_seq = 0, fq_qual = 0;
+    bool partial = false, open = false; std::string name; uint64_t n_rec = 0;
+    auto first_word = [&](size_t n) { size_t e = 1; while (e < n && line[e] != ' ' && line[e] != '\t') ++e; name.assign(line.data() + 1, e - 1); };
+    auto close = [&]() { if (open) { on_seq(name); open = false; } };
+    while (gzgets(f, line.data(), (int)line.size())) {
+        size_t n = strlen(line.data());
+        const bool complete = n && line[n - 1] == '\n';
+        while (n && (line[n - 1] == '\n' || line[n - 1] == '\r')) --n;
+        const bool starts_line = !partial;
+        partial = !complete;
+        if (fmt == 0 && starts_line && n) fmt = line[0] == '@' ? 2 : 1;
+        if (fmt == 2) {
+            if (starts_line) {
+                if (fq_state == 0) {
+                    if (!n) fq_kind = 0;
+                    else if (line[0] == '@') { fq_kind = 'H'; first_word(n); open = true; ++n_rec; }
+                    else { gzclose(f); usage_error("malformed FASTQ record in " + path + " (sequence " + std::to_string(n_rec + 1) + "): '@' expected"); }
+                } else if (fq_state == 1) fq_kind = (n && line[0] == '+') ? 'P' : 'S';
+                else fq_kind = 'Q';
+            }
+            if (fq_kind == 'S') { bases.append(line.data(), n); fq_seq += n; }
+            else if (fq_kind == 'Q') fq_qual += n;
+            if (complete) {
+                if (fq_kind == 'H') { fq_state = 1; fq_seq = 0; }
+                else if (fq_kind == 'P') { close(); fq_state = 2; fq_qual = 0; }
+                else if (fq_kind == 'Q' && fq_qual >= fq_seq) fq_state = 0;
+            }
+        } else {
+            if (starts_line && n && line[0] == '>') { close(); first_word(n); open = true; ++n_rec; }
+            else if (!(starts_line && n && line[0] == ';') && open) bases.append(line.data(), n);
+            else if (starts_line && n && line[0] != ';' && !open) { gzclose(f); usage_error(path + ": sequence data before the first '>' header"); }
+        }
+    }
+    int zerr = Z_OK; const char* zmsg = gzerror(f, &zerr);
+    if (zerr != Z_OK && zerr != Z_STREAM_END) { const std::string m = zmsg ? zmsg : "read error"; gzclose(f); usage_error(path + ": " + m); }
+    gzclose(f);
+    close();
+}
+int query_mode(const Options& o, const std::string& prefix, int threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = clk::now();
+    const std::string fa = prefix + ".unitigs.fa", tsv = prefix + ".query.tsv";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-query", F);
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F);
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    F.seq.reset(); F.slices.clear(); F.mp.reset();                 // (the set is resident: the host copy is not needed again)
+    const auto t1 = clk::now();
+    check(cdbg_index(ctx));
+    const auto t2 = clk::now();
+    // written beside the target and renamed over it: a failure leaves an earlier table as it was
+    struct TmpOut {
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+    } tmp;
+    tmp.name = tsv + ".tmp" + std::to_string((long)getpid());
+    tmp.f = fopen(tmp.name.c_str(), "w");
+    if (!tmp.f) { const std::string n = tmp.name; tmp.name.clear(); usage_error("cannot write " + n); }
+    const uint64_t BATCH = 64ull << 20, K = (uint64_t)o.k;
+    std::string bases, out; std::vector<std::string> names; std::vector<uint64_t> off{ 0 }, hits;
+    uint64_t n_seqs = 0, n_kmers = 0, n_found = 0; double query_s = 0; bool wfail = false;
+    auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+    auto flush = [&]() {
+        if (names.empty()) return;
+        hits.resize(std::max<size_t>(bases.size(), 1));
+        const auto q0 = clk::now();
+        check(cdbg_query(ctx, bases.data(), off.data(), names.size(), hits.data()));
+        query_s += secs(q0, clk::now());
+        out.clear();
+        for (size_t i = 0; i < names.size(); ++i) {
+            const uint64_t b = off[i], len = off[i + 1] - b, nk = len >= K ? len - K + 1 : 0;
+            uint64_t found = 0, runs = 0;
+            const size_t head = out.size();
+            std::string rs;
+            uint64_t r_q = 0, r_len = 0, r_u = 0, r_o = 0, r_s = 0, last_o = 0;
+            auto close_run = [&]() {
+                if (!r_len) return;
+                if (runs++) rs.push_back(',');
+                put_u(rs, r_q); rs.push_back(':'); put_u(rs, r_len); rs.push_back(':'); put_u(rs, r_u); rs.push_back(':'); rs.push_back(r_s ? '-' : '+'); rs.push_back(':'); put_u(rs, r_o);
+                r_len = 0;
+            };
+            for (uint64_t p = 0; p < nk; ++p) {
+                const uint64_t h = hits[b + p];
+                if (h == ~0ull) { close_run(); continue; }
+                ++found;
+                const uint64_t u = h >> 33, uo = (h >> 1) & 0xFFFFFFFFull, st = h & 1;
+                if (r_len && u == r_u && st == r_s && uo == (st ? last_o - 1 : last_o + 1)) { ++r_len; last_o = uo; continue; }
+                close_run();
+                r_q = p; r_len = 1; r_u = u; r_o = uo; r_s = st; last_o = uo;
+            }
+            close_run();
+            (void)head;
+            out.append(names[i]); out.push_back('\t'); put_u(out, nk); out.push_back('\t'); put_u(out, found); out.push_back('\t');
+            if (runs) out.append(rs); else out.push_back('*');
+            out.push_back('\n');
+            n_kmers += nk; n_found += found;
+        }
+        if (fwrite(out.data(), 1, out.size(), tmp.f) != out.size()) wfail = true;
+        n_seqs += names.size();
+        names.clear(); bases.clear(); off.assign(1, 0);
+    };
+    parse_queries(o.query, bases, [&](const std::string& name) {
+        if (bases.size() > BATCH && !names.empty()) {              // this record would pass 64 MB of bases: what came before it goes first
+            const std::string last = bases.substr(off.back());
+            bases.resize(off.back());
+            flush();
+            bases = last;
+        }
+        names.push_back(name); off.push_back(bases.size());
+    });
+    flush();
+    { FILE* g = tmp.f; tmp.f = nullptr; if (fclose(g) != 0) wfail = true; }
+    if (wfail) usage_error("write error on " + tmp.name);
+    if (rename(tmp.name.c_str(), tsv.c_str()) != 0) usage_error("cannot rename " + tmp.name + " to " + tsv);
+    tmp.name.clear();
+    printf("query: %llu sequences, %llu k-mers, %llu found (load %.2f s, index %.2f s, query %.2f s)\n", (unsigned long long)n_seqs,
+           (unsigned long long)n_kmers, (unsigned long long)n_found, secs(t0, t1), secs(t1, t2), query_s);
+    printf("hits written to %s\n", tsv.c_str());
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -648,7 +798,9 @@ int main(int argc, char** argv) {
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
-        if (o.redo_links) {
+        if (!o.query.empty() && o.redo_links) usage_error("-query and -redo-links are two modes: give one of them");
+        if (!o.query.empty() && o.n_gpus != 1) usage_error("-query runs on one GPU: -nb-gpus must be 1");
+        if (o.redo_links || !o.query.empty()) {
             if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
             const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
             if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
@@ -656,6 +808,7 @@ int main(int argc, char** argv) {
                 prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
             }
             int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            if (!o.query.empty()) return query_mode(o, prefix, std::max(1, std::min(threads, 60)));
             return redo_links(o, prefix, std::max(1, std::min(threads, 60)));
         }
         auto t0 = std::chrono::steady_clock::now();

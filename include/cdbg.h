@@ -274,6 +274,34 @@ int cdbg_unitig_id_base(cdbg_ctx* ctx, uint64_t* first_id, uint64_t* total);
  * (at most 2^31 slots, one key per end at two thirds full). */
 int cdbg_load_unitigs(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_unitigs, const uint64_t* kc);
 
+/* Node lookup: where is this k-mer -- which unitig, at which offset, on which strand -- or is it not in the graph at all.  Valid after
+ * cdbg_glue / cdbg_run and after cdbg_load_unitigs, on one rank (world_size == 1; CDBG_E_STATE otherwise: a rank that holds a share of
+ * the unitigs cannot answer for the graph; CDBG_E_STATE too before cdbg_glue).
+ * cdbg_index builds the index of the resident unitig set, or keeps the one that is there: an open-address table in HBM of 64-bit slots
+ * that hold POSITIONS -- (unitig << 32) | offset, the key of a slot is the k-mer the resident 2-bit arena spells there -- of the smallest
+ * power of two >= 1.5 P + 64 slots for the P = sum(LN - k + 1) k-mer positions of the set: 8 bytes per slot for every k
+ * (bcalm_amd/csrc/k_index.h).  A table that does not fit is CDBG_E_NOMEM, with the sizes in the message.  cdbg_reset, a new cdbg_glue
+ * and a new cdbg_load_unitigs forget the index and hand its memory back.
+ * cdbg_index_info (builds the index when it is not there): out[0] = k-mer positions P, out[1] = distinct k-mers, out[2] = slots,
+ * out[3] = bytes of the table.  The unitigs of a graph spell every k-mer once: out[0] == out[1] == n_solid; a loaded set may repeat k-mers.
+ * cdbg_query (builds the index when it is not there): host ASCII as cdbg_load_unitigs takes it -- sequence i is
+ * bases[offsets[i] .. offsets[i+1]), offsets[0] may be non-zero -- and ONE 64-bit word per base: hits[p - offsets[0]] for the k-mer that
+ * starts at bases[p]; the caller provides offsets[n_seqs] - offsets[0] words.  n_seqs == 0, or no bases: nothing is written.
+ *   hit word           UINT64_MAX = not in the set; otherwise (unitig << 33) | (offset << 1) | strand: unitig = the position in the order of
+ *                      cdbg_fetch_unitigs, offset = the first base of the k-mer inside that unitig, strand 0 = the unitig reads there as
+ *                      the query k-mer, 1 = as its reverse complement; a k-mer that is its own reverse complement (even k) reports 0.
+ *                      With all_abundance_counts the abundance of a hit is ab[ab_off[unitig] + offset] of cdbg_fetch_unitig_abundances.
+ *   smallest occurrence  a k-mer that the set spells more than once (loaded sets: repeated records, pieces that overlap, any foreign
+ *                      FASTA) reports the smallest (unitig, offset) of its occurrences, and the strand relative to THAT occurrence.
+ *   boundaries         bytes outside ACGTacgt break every window that contains them, and every window that does not lie wholly inside one
+ *                      sequence is a miss: the last k - 1 positions of each sequence, sequences shorter than k, windows across two
+ *                      adjacent sequences whatever the concatenated bytes spell.
+ * Device memory per call is bounded: the input is walked in batches of 64 M bases (consecutive batches overlap by k - 1 bases: a sequence
+ * may span any number of them) through the pinned staging, and each batch's hits are copied into `hits`. */
+int cdbg_index(cdbg_ctx* ctx);
+int cdbg_index_info(cdbg_ctx* ctx, uint64_t out[4]);
+int cdbg_query(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t* hits);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
@@ -287,7 +315,10 @@ int cdbg_load_unitigs(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets,
  *   CDBG_GLUE_REPLICATED=1        the replicated glue exchange for emit_replicated = 0 as well       CDBG_HOST_MARKS=1  wall-clock marks between host-side phases (stderr)
  *   CDBG_POISON_ALLOC=<byte>      every device block newly obtained without a request for zeroing (fresh, or from the process's pool) is
  *                                 filled with that byte (0xFF, 0xA5, ...): no kernel may depend on what a buffer held before.  Read for every
- *                                 new block, never on the path that keeps an existing allocation */
+ *                                 new block, never on the path that keeps an existing allocation
+ *   CDBG_QUERY_BATCH=<n>          cdbg_query: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
+ *   CDBG_INDEX_LOG2_SLOTS=<n>     cdbg_index: a table of 2^n slots, floored at the smallest power of two > distinct k-mers (and never larger
+ *                                 than the default): long probe runs that wrap around the table's end */
 
 #ifdef __cplusplus
 }
