@@ -43,12 +43,13 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-ABI_VERSION = 7                                        # include/cdbg.h CDBG_ABI_VERSION this binding was written for
+ABI_VERSION = 8                                        # include/cdbg.h CDBG_ABI_VERSION this binding was written for
 EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy", "cdbg_release_cached", "cdbg_last_error", "cdbg_push_reads", "cdbg_push_text",
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
            "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
+           "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -115,6 +116,9 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_index.argtypes = [vp]
     lib.cdbg_index_info.argtypes = [vp, C.POINTER(u64)]
     lib.cdbg_query.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
+    lib.cdbg_quantify.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
+    lib.cdbg_fetch_quant.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
+    lib.cdbg_quant_reset.argtypes = [vp]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -255,6 +259,53 @@ class Graph:
                 row.append(None if h == self.MISS else (h >> 33, (h >> 1) & 0xFFFFFFFF, "-" if h & 1 else "+"))
             out.append(row)
         return out
+
+    # ---- quantification of a read set against the resident unitigs (cdbg_quantify / cdbg_fetch_quant / cdbg_quant_reset) ----
+    def quantify(self, seqs, first_offset=0) -> dict:
+        """count the k-mers of `seqs` (str / bytes; any bytes, any lengths) at the positions of the resident unitigs that spell them; the
+        counts ACCUMULATE over calls.  -> {windows, found, extended} of this call: valid k-mer windows, those in the set, and those of them
+        answered from the neighbouring hit without a probe"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = first_offset
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        out = (C.c_uint64 * 3)()
+        self._ck(self.lib.cdbg_quantify(self._h, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), out))
+        return {"windows": out[0], "found": out[1], "extended": out[2]}
+
+    def quant_raw(self, per_kmer=True):
+        """-> (kc, covered, ab, ab_off) as ctypes arrays over all unitigs (ab, ab_off None without per_kmer): no Python object per k-mer"""
+        self._ck(self.lib.cdbg_fetch_quant(self._h, 0, 0, None, None, None, None))       # (the call's own refusal, under its own name)
+        n, tb = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.cdbg_num_unitigs(self._h, C.byref(n), C.byref(tb)))
+        n, tb = n.value, tb.value
+        kc = (C.c_uint64 * max(n, 1))()
+        cov = (C.c_uint32 * max(n, 1))()
+        ab = (C.c_uint32 * max(tb, 1))() if per_kmer else None
+        off = (C.c_uint64 * (n + 1))() if per_kmer else None
+        self._ck(self.lib.cdbg_fetch_quant(self._h, 0, n, kc, cov, ab, off))
+        return kc, cov, ab, off
+
+    def quant(self, per_kmer=False):
+        """-> per unitig (same order as unitigs()) (kc, covered): the sum of its positions' counts and the positions counted at least
+        once; per_kmer: (kc, covered, [count per k-mer position, in the orientation of the sequence])"""
+        kc, cov, ab, off = self.quant_raw(per_kmer)
+        n = (len(off) - 1) if per_kmer else self._num_unitigs()
+        if per_kmer:
+            return [(kc[i], cov[i], list(ab[off[i]:off[i + 1]])) for i in range(n)]
+        return [(kc[i], cov[i]) for i in range(n)]
+
+    def quant_reset(self):
+        """zero the counts; the index stays"""
+        self._ck(self.lib.cdbg_quant_reset(self._h))
+
+    def _num_unitigs(self):
+        n, tb = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.cdbg_num_unitigs(self._h, C.byref(n), C.byref(tb)))
+        return n.value
 
     def generate_reads(self, n_reads, read_len, cfg, first_read=0, total_reads=None):
         total = n_reads if total_reads is None else total_reads

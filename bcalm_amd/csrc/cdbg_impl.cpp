@@ -38,6 +38,7 @@
 #include "k_compact_wave.h"
 #include "k_split.h"
 #include "k_index.h"
+#include "k_quant.h"
 
 using namespace cdbg;
 
@@ -49,6 +50,7 @@ using namespace cdbg;
 #include "host_glue.h"
 #include "host_relink.h"
 #include "host_index.h"
+#include "host_quant.h"
 
 
 // =======================================================================================
@@ -262,6 +264,22 @@ int cdbg_query(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t
     if (!c || (n_seqs && (!offsets || !bases || !hits))) return fail(CDBG_E_PARAM, "null argument");
     (void)hipSetDevice(c->prm.device_id);
     try { DISPATCH_WA(query_impl, c, bases, offsets, n_seqs, hits) } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_query: out of host memory"); }
+}
+// ---- quantification of a read set against the resident unitigs (k_quant.h, host_quant.h) ----
+int cdbg_quantify(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[3]) {
+    if (!c || !out || (n_seqs && (!offsets || !bases))) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(quantify_impl, c, bases, offsets, n_seqs, out) } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_quantify: out of host memory"); }
+}
+int cdbg_fetch_quant(cdbg_ctx* c, uint64_t first, uint64_t n, uint64_t* kc, uint32_t* covered, uint32_t* ab, uint64_t* ab_off) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    try { return fetch_quant_impl(c, first, n, kc, covered, ab, ab_off); } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_fetch_quant: out of host memory"); }
+}
+int cdbg_quant_reset(cdbg_ctx* c) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return quant_reset_impl(c);
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");

@@ -239,7 +239,7 @@ int glue_table_slots(uint64_t want, uint32_t* out) {
 struct Knobs {
     std::vector<std::pair<std::string, std::string>> kv;
     void snapshot() {
-        static const char* const NAMES[] = { "CDBG_POISON_ALLOC", "CDBG_MAX_PASSES", "CDBG_CW_TIER3", "CDBG_CW_TIER2", "CDBG_SCAN_TWO_LEVEL", "CDBG_COUNT_MAX_SUB", "CDBG_VAR_RESAMPLE", "CDBG_EXACT_NO_CUR32", "CDBG_SOLID_FIRST_TINY", "CDBG_PREWARM_MIN_BYTES", "CDBG_NO_PREWARM", "CDBG_DEBUG_SEGHIST", "CDBG_FAST_MAX_RECORDS", "CDBG_FAST_SKIP2_Q8", "CDBG_FAST_SKIP_Q8", "CDBG_FORCE_MULTI", "CDBG_GENERIC_SCAN", "CDBG_GLUE_LOG", "CDBG_GLUE_RANK", "CDBG_GLUE_REPLICATED", "CDBG_GLUE_TABLE", "CDBG_JOIN_LOG_JB", "CDBG_NO_COUNT_TIER2", "CDBG_NO_SIFT", "CDBG_NO_SPLIT", "CDBG_PART_CAP", "CDBG_REPAIR_MAX_PASSES", "CDBG_SCAN_MODE", "CDBG_STAGE_BYTES", "CDBG_STREAM_BATCH_TILES", "CDBG_STREAM_MIN_BYTES", "CDBG_VAR_SCALE", "CDBG_WALK_MAX", "CDBG_DEFER_SLICES", "CDBG_DEFER_CAP", "CDBG_PLACE_GRID", "CDBG_BIG_ONE_WG", "CDBG_QUERY_BATCH", "CDBG_INDEX_LOG2_SLOTS" };
+        static const char* const NAMES[] = { "CDBG_POISON_ALLOC", "CDBG_MAX_PASSES", "CDBG_CW_TIER3", "CDBG_CW_TIER2", "CDBG_SCAN_TWO_LEVEL", "CDBG_COUNT_MAX_SUB", "CDBG_VAR_RESAMPLE", "CDBG_EXACT_NO_CUR32", "CDBG_SOLID_FIRST_TINY", "CDBG_PREWARM_MIN_BYTES", "CDBG_NO_PREWARM", "CDBG_DEBUG_SEGHIST", "CDBG_FAST_MAX_RECORDS", "CDBG_FAST_SKIP2_Q8", "CDBG_FAST_SKIP_Q8", "CDBG_FORCE_MULTI", "CDBG_GENERIC_SCAN", "CDBG_GLUE_LOG", "CDBG_GLUE_RANK", "CDBG_GLUE_REPLICATED", "CDBG_GLUE_TABLE", "CDBG_JOIN_LOG_JB", "CDBG_NO_COUNT_TIER2", "CDBG_NO_SIFT", "CDBG_NO_SPLIT", "CDBG_PART_CAP", "CDBG_REPAIR_MAX_PASSES", "CDBG_SCAN_MODE", "CDBG_STAGE_BYTES", "CDBG_STREAM_BATCH_TILES", "CDBG_STREAM_MIN_BYTES", "CDBG_VAR_SCALE", "CDBG_WALK_MAX", "CDBG_DEFER_SLICES", "CDBG_DEFER_CAP", "CDBG_PLACE_GRID", "CDBG_BIG_ONE_WG", "CDBG_QUERY_BATCH", "CDBG_INDEX_LOG2_SLOTS", "CDBG_QUANT_CEILING", "CDBG_QUANT_CLAMP_WINDOWS", "CDBG_QUANT_NO_EXTEND" };
         for (const char* n : NAMES) if (const char* e = getenv(n)) kv.emplace_back(n, e);
     }
     const char* get(const char* name) const { for (const auto& p : kv) if (p.first == name) return p.second.c_str(); return nullptr; }
@@ -320,6 +320,10 @@ struct cdbg_ctx {
     // node lookup (host_index.h): the position table over the resident set -- [0] k-mer positions [1] distinct k-mers [2] slots [3] bytes -- and the per-batch buffers of cdbg_query
     DBuf<uint64_t> index_slots; bool indexed = false; uint64_t index_info[4] = { 0, 0, 0, 0 };
     DBuf<uint8_t> q_text; DBuf<uint32_t> q_bnd; DBuf<uint64_t> q_hits, q_prof;
+    // quantification (host_quant.h): kmer_off[U + 1] = the first k-mer position of every unitig in the set's numbering (built with the index), one counter
+    // per position, the windows added since the counters were last clamped, and the buffers of cdbg_quantify's totals and cdbg_fetch_quant's read-out
+    DBuf<uint64_t> kmer_off; DBuf<uint32_t> quant_cnt; bool quant_ready = false; uint64_t quant_tally = 0;
+    DBuf<uint64_t> quant_out, quant_kc; DBuf<uint32_t> quant_cov, quant_rep;
     DBuf<uint4> rank_a, rank_b; DBuf<uint32_t> rank_flag;
     DBuf<uint4> walk_rec; DBuf<uint32_t> walk_heads, walk_hlen; DBuf<uint64_t> walk_hoff; bool walk_off = false;   // chains walked from their heads (k_walk.h); walk_off: a run of this context had a chain the walk does not take
     // multi-GPU: transport (RCCL or caller-supplied) and the record exchange buffers

@@ -6,7 +6,8 @@ namespace {
 
 // whatever replaces the resident set forgets its index: the table goes back to the pool
 void index_forget(cdbg_ctx* c) {
-    c->indexed = false; c->index_slots.release();
+    c->indexed = false; c->index_slots.release(); c->kmer_off.release();
+    c->quant_ready = false; c->quant_tally = 0; c->quant_cnt.release();      // the counters of cdbg_quantify go with the table (host_quant.h)
     for (uint64_t& v : c->index_info) v = 0;
 }
 
@@ -23,7 +24,8 @@ int index_impl(cdbg_ctx* c, const char* what) {
     if (c->indexed) return CDBG_OK;
     hipStream_t s = c->stream;
     const uint64_t U = c->n_unitigs;
-    DBuf<uint32_t> kcount; DBuf<uint64_t> kmer_off, out;
+    DBuf<uint32_t> kcount; DBuf<uint64_t> out;
+    DBuf<uint64_t>& kmer_off = c->kmer_off;                  // kept with the table: the numbering of cdbg_quantify's counters
     CK(kcount.alloc(U, false)); CK(kmer_off.alloc(U + 1, false)); CK(out.alloc(4, false));
     IndexParams ip{};
     ip.n_unitigs = U; ip.k = c->k; ip.unitig_off = c->unitig_off.p; ip.unitig_len = c->unitig_len.p; ip.packed = c->unitig_packed.p;

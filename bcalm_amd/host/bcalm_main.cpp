@@ -13,6 +13,9 @@
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -query queries.fa[.gz] [-out prefix]
 //     reads <prefix>.unitigs.fa, looks every k-mer of the query sequences up in it (cdbg_load_unitigs + cdbg_index + cdbg_query) and
 //     writes <prefix>.query.tsv: name, k-mers, k-mers found, runs qpos:len:unitig:strand:upos.
+//   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -quantify sample.fq[.gz] [-all-abundance-counts] [-out prefix]
+//     reads <prefix>.unitigs.fa, counts the k-mers of the sample at the unitig positions that spell them (cdbg_load_unitigs + cdbg_quantify +
+//     cdbg_fetch_quant) and writes <prefix>.quant.tsv: unitig, k-mers, KC, covered k-mers, km [, the per-position counts].
 // Everything between parsing and writing is three calls into libcdbg.so (include/cdbg.h):
 // this file is the replacement for bcalm_1::execute()/Functor (src/bcalm_1.cpp:49-97).
 #include <zlib.h>
@@ -53,10 +56,12 @@ struct Options {
     bool gfa = false, verbose = false, all_ab = false, no_stream = false;
     bool redo_links = false, skip_bcalm = false, skip_bglue = false;   // -redo-links: only the link step, on an existing <prefix>.unitigs.fa
     std::string solid_out;
+    std::string quantify;                            // -quantify <file>: count the k-mers of its sequences per unitig of an existing <prefix>.unitigs.fa
     std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
 
 [[noreturn]] void usage_error(const std::string& msg) { throw std::runtime_error(msg); }
+void put_km(std::string& d, double km) { char t[48]; const int n = snprintf(t, sizeof t, "%.1f", km); d.append(t, (size_t)n); }   // the reference's %.1f
 
 Options parse(int argc, char** argv) {
     Options o;
@@ -77,6 +82,7 @@ Options parse(int argc, char** argv) {
         else if (a == "-gfa") o.gfa = true;
         else if (a == "-redo-links") o.redo_links = true;             // the reference's hidden option: scripts/pufferize.py:143 tells its users to run it
         else if (a == "-query") o.query = need("-query");
+        else if (a == "-quantify") o.quantify = need("-quantify");
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -659,9 +665,9 @@ int redo_links(const Options& o, const std::string& prefix, int threads) {
 // the tolerant serial reader of parse_stream with the record names kept: FASTA / FASTQ, plain or gzip, sequences and qualities may wrap;
 // on_seq(name) is called when a record's sequence is complete and lies at the end of `bases`
 template <class F>
-void parse_queries(const std::string& path, std::string& bases, F&& on_seq) {
+void parse_queries(const std::string& path, std::string& bases, F&& on_seq, const char* what = "query file") {
     gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) usage_error("cannot open query file " + path);
+    if (!f) usage_error(std::string("cannot open ") + what + " " + path);
     gzbuffer(f, 1 << 20);
     std::vector<char> line(1 << 22);
     int fmt = 0, fq_state = 0; char fq_kind = 0; uint64_t fq_seq = 0, fq_qual = 0;
@@ -785,6 +791,81 @@ int query_mode(const Options& o, const std::string& prefix, int threads) {
     return EXIT_SUCCESS;
 }
 
+// ---- -quantify: the k-mers of a sample counted per unitig (cdbg_load_unitigs + cdbg_quantify + cdbg_fetch_quant) ----
+int quantify_mode(const Options& o, const std::string& prefix, int threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = clk::now();
+    const std::string fa = prefix + ".unitigs.fa", tsv = prefix + ".quant.tsv";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-quantify", F);
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F);
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    const uint64_t nu = F.nu, K = (uint64_t)o.k;
+    std::vector<uint64_t> nk(nu ? nu : 1);                         // k-mer positions per unitig, file order
+    uint64_t n_pos = 0;
+    for (uint64_t i = 0; i < nu; ++i) { nk[i] = F.off[i + 1] - F.off[i] - K + 1; n_pos += nk[i]; }
+    F.seq.reset(); F.slices.clear(); F.mp.reset();                 // (the set is resident: the host copy is not needed again)
+    const auto t1 = clk::now();
+    check(cdbg_index(ctx));
+    const auto t2 = clk::now();
+    // written beside the target and renamed over it: a failure leaves an earlier table as it was
+    struct TmpOut {
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+    } tmp;
+    tmp.name = tsv + ".tmp" + std::to_string((long)getpid());
+    tmp.f = fopen(tmp.name.c_str(), "w");
+    if (!tmp.f) { const std::string n = tmp.name; tmp.name.clear(); usage_error("cannot write " + n); }
+    const uint64_t BATCH = 64ull << 20;
+    std::string bases; std::vector<uint64_t> off{ 0 };
+    uint64_t n_seqs = 0, tot[3] = { 0, 0, 0 }; double quant_s = 0;
+    auto flush = [&]() {
+        if (off.size() == 1) return;
+        uint64_t out[3];
+        const auto q0 = clk::now();
+        check(cdbg_quantify(ctx, bases.data(), off.data(), off.size() - 1, out));
+        quant_s += secs(q0, clk::now());
+        for (int i = 0; i < 3; ++i) tot[i] += out[i];
+        n_seqs += off.size() - 1;
+        bases.clear(); off.assign(1, 0);
+    };
+    parse_queries(o.quantify, bases, [&](const std::string&) {
+        if (bases.size() > BATCH && off.size() > 1) {              // this record would pass 64 MB of bases: what came before it goes first
+            const std::string last = bases.substr(off.back());
+            bases.resize(off.back());
+            flush();
+            bases = last;
+        }
+        off.push_back(bases.size());
+    }, "sample file");
+    flush();
+    if (!n_seqs) { uint64_t out[3]; const uint64_t z[1] = { 0 }; check(cdbg_quantify(ctx, "", z, 0, out)); }
+    std::vector<uint64_t> kc(nu ? nu : 1), aboff(nu + 1); std::vector<uint32_t> cov(nu ? nu : 1), ab(o.all_ab ? n_pos + 1 : 1);
+    const auto f0 = clk::now();
+    check(cdbg_fetch_quant(ctx, 0, nu, kc.data(), cov.data(), o.all_ab ? ab.data() : nullptr, o.all_ab ? aboff.data() : nullptr));
+    quant_s += secs(f0, clk::now());
+    auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+    bool wfail = false; std::string out;
+    for (uint64_t i = 0; i < nu; ++i) {
+        put_u(out, i); out.push_back('\t'); put_u(out, nk[i]); out.push_back('\t'); put_u(out, kc[i]); out.push_back('\t'); put_u(out, cov[i]); out.push_back('\t');
+        put_km(out, (double)kc[i] / (double)nk[i]);
+        if (o.all_ab) {
+            out.push_back('\t');
+            for (uint64_t j = aboff[i]; j < aboff[i + 1]; ++j) { if (j > aboff[i]) out.push_back(','); put_u(out, ab[j]); }
+        }
+        out.push_back('\n');
+        if (out.size() > (1u << 22) || i + 1 == nu) { if (fwrite(out.data(), 1, out.size(), tmp.f) != out.size()) wfail = true; out.clear(); }
+    }
+    { FILE* g = tmp.f; tmp.f = nullptr; if (fclose(g) != 0) wfail = true; }
+    if (wfail) usage_error("write error on " + tmp.name);
+    if (rename(tmp.name.c_str(), tsv.c_str()) != 0) usage_error("cannot rename " + tmp.name + " to " + tsv);
+    tmp.name.clear();
+    printf("quantify: %llu sequences, %llu k-mers, %llu found, %llu extended (load %.2f s, index %.2f s, quantify %.2f s)\n", (unsigned long long)n_seqs,
+           (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], secs(t0, t1), secs(t1, t2), quant_s);
+    printf("counts written to %s\n", tsv.c_str());
+    return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -798,9 +879,11 @@ int main(int argc, char** argv) {
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
+        if (!o.quantify.empty() && (!o.query.empty() || o.redo_links)) usage_error("-quantify, -query and -redo-links are separate modes: give one of them");
+        if (!o.quantify.empty() && o.n_gpus != 1) usage_error("-quantify runs on one GPU: -nb-gpus must be 1");
         if (!o.query.empty() && o.redo_links) usage_error("-query and -redo-links are two modes: give one of them");
         if (!o.query.empty() && o.n_gpus != 1) usage_error("-query runs on one GPU: -nb-gpus must be 1");
-        if (o.redo_links || !o.query.empty()) {
+        if (o.redo_links || !o.query.empty() || !o.quantify.empty()) {
             if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
             const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
             if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
@@ -808,6 +891,7 @@ int main(int argc, char** argv) {
                 prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
             }
             int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            if (!o.quantify.empty()) return quantify_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.query.empty()) return query_mode(o, prefix, std::max(1, std::min(threads, 60)));
             return redo_links(o, prefix, std::max(1, std::min(threads, 60)));
         }
@@ -925,7 +1009,6 @@ int main(int argc, char** argv) {
             std::atomic<uint64_t> next_block{0};
             std::mutex wm; std::condition_variable wcv; uint64_t turn = 0; bool wfail = false;
             auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
-            auto put_km = [](std::string& d, double km) { char t[48]; const int n = snprintf(t, sizeof t, "%.1f", km); d.append(t, (size_t)n); };
             auto writer = [&]() {
                 std::string fb, gb;
                 for (;;) {

@@ -85,7 +85,7 @@ typedef struct cdbg_stats_t {
 /* ABI version: bumped whenever a struct of this header changes.  From version 5 on cdbg_stats_t only ever GROWS AT ITS END;
  * a binding checks cdbg_abi_version() against the header it was written for and sizeof(cdbg_stats_t) against
  * cdbg_stats_sizeof() when it loads the library (bcalm_amd/api.py does), instead of reading fields at stale offsets. */
-#define CDBG_ABI_VERSION 7
+#define CDBG_ABI_VERSION 8
 int cdbg_abi_version(void);
 uint64_t cdbg_stats_sizeof(void);
 
@@ -302,6 +302,29 @@ int cdbg_index(cdbg_ctx* ctx);
 int cdbg_index_info(cdbg_ctx* ctx, uint64_t out[4]);
 int cdbg_query(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t* hits);
 
+/* Quantification: how often does a SECOND read set spell the k-mer at every position of every resident unitig, and how much of each
+ * unitig does it cover -- the per-sample KC / km / ab:Z: of the header grammar.  Preconditions as for cdbg_query (after cdbg_glue /
+ * cdbg_run or cdbg_load_unitigs, one rank; CDBG_E_STATE otherwise).  The library keeps one 32-bit counter per k-mer position of the
+ * set (4 bytes x P beside the index; counters that do not fit are CDBG_E_NOMEM, with the sizes in the message), zeroed when created;
+ * cdbg_reset, a new cdbg_glue and a new cdbg_load_unitigs forget them with the index.
+ * cdbg_quantify (builds the index and the counters when they are not there): input as cdbg_query takes it -- offsets[0] may be non-zero;
+ *   empty sequences, sequences shorter than k and bytes outside ACGTacgt are legal.  Every window of k bases that lies wholly inside one
+ *   sequence and holds only ACGTacgt adds 1 to the counter of the position cdbg_query reports for it (either strand; in a loaded set
+ *   the smallest occurrence); a window that misses adds nothing.  The call ACCUMULATES: two calls equal one call over the concatenated
+ *   input.  out (per call, not NULL): out[0] = windows looked at, out[1] = windows found, out[2] = of those, windows answered from the
+ *   neighbouring hit without a probe (bcalm_amd/csrc/k_quant.h; 0 in a set that repeats k-mers).  n_seqs == 0, or no bases: the index
+ *   and the counters are built, out = {0, 0, 0}.  Device memory per call is bounded as for cdbg_query, with nothing stored per base.
+ * cdbg_fetch_quant, unitigs [first, first + n) in the order of cdbg_fetch_unitigs: kc[i] = the sum of the unitig's reported counts,
+ *   covered[i] = its positions with a count >= 1 (each may be NULL); ab and ab_off both non-NULL: the per-position counts in the layout
+ *   of cdbg_fetch_unitig_abundances -- ab_off[n + 1], LN - k + 1 values per unitig in the orientation of its sequence.  Before any
+ *   cdbg_quantify since the set became resident: zeros.
+ * cdbg_quant_reset zeroes the counters and keeps the index.
+ * Counts follow the abundance rule above: exact below 2^31 - 4096, reported as 2147483647 from there on; kc sums the reported values.
+ * (The counters are clamped to that ceiling before 2^31 more windows could be added: none ever wraps.) */
+int cdbg_quantify(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[3]);
+int cdbg_fetch_quant(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint64_t* kc, uint32_t* covered, uint32_t* ab, uint64_t* ab_off);
+int cdbg_quant_reset(cdbg_ctx* ctx);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
@@ -318,7 +341,11 @@ int cdbg_query(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64
  *                                 new block, never on the path that keeps an existing allocation
  *   CDBG_QUERY_BATCH=<n>          cdbg_query: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
  *   CDBG_INDEX_LOG2_SLOTS=<n>     cdbg_index: a table of 2^n slots, floored at the smallest power of two > distinct k-mers (and never larger
- *                                 than the default): long probe runs that wrap around the table's end */
+ *                                 than the default): long probe runs that wrap around the table's end
+ *   CDBG_QUANT_CLAMP_WINDOWS=<n>  cdbg_quantify: clamp the counters before more than n windows (default and at most 2^31) were added since the last clamp
+ *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify: every window probes the index (out[2] = 0)
+ *   CDBG_QUANT_CEILING=<n>        cdbg_quantify / cdbg_fetch_quant: counts are exact below n (default and at most 2^31 - 4096) and reported as 2147483647
+ *                                 from there on.  THE ONE HOOK THAT CHANGES REPORTED VALUES: it brings the saturation rule within reach of a test */
 
 #ifdef __cplusplus
 }
