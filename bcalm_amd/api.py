@@ -43,13 +43,13 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-ABI_VERSION = 8                                        # include/cdbg.h CDBG_ABI_VERSION this binding was written for
+ABI_VERSION = 9                                        # include/cdbg.h CDBG_ABI_VERSION this binding was written for
 EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy", "cdbg_release_cached", "cdbg_last_error", "cdbg_push_reads", "cdbg_push_text",
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
            "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
-           "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset",
+           "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset", "cdbg_thread", "cdbg_fetch_runs",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -119,6 +119,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_quantify.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
     lib.cdbg_fetch_quant.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
     lib.cdbg_quant_reset.argtypes = [vp]
+    lib.cdbg_thread.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
+    lib.cdbg_fetch_runs.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -301,6 +303,37 @@ class Graph:
     def quant_reset(self):
         """zero the counts; the index stays"""
         self._ck(self.lib.cdbg_quant_reset(self._h))
+
+    # ---- run-length lookup: the walk of sequences through the resident unitigs (cdbg_thread / cdbg_fetch_runs) ----
+    def thread_raw(self, seqs, first_offset=0):
+        """-> (totals, run_off, start, place, len): {windows, found, runs, extended} of the call and the runs as ctypes arrays -- run_off[n + 1]
+        per sequence, and per run its first position in the concatenated sequences, the hit word of that position (unitig << 33 | offset << 1
+        | strand) and its length in windows.  No Python object per k-mer or per run.  first_offset as query_raw takes it"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = first_offset
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.cdbg_thread(self._h, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), out))
+        runs = out[2]
+        run_off = (C.c_uint64 * (len(bs) + 1))()
+        start, place, ln = (C.c_uint64 * max(runs, 1))(), (C.c_uint64 * max(runs, 1))(), (C.c_uint32 * max(runs, 1))()
+        self._ck(self.lib.cdbg_fetch_runs(self._h, run_off, start, place, ln))
+        return {"windows": out[0], "found": out[1], "runs": runs, "extended": out[3]}, run_off, start, place, ln
+
+    def thread(self, seqs):
+        """-> per sequence the list of its runs (q, unitig, offset, strand, n): n consecutive k-mers from the sequence's window q on lie on
+        `unitig` from `offset` on, upwards on strand "+" (the unitig reads as the sequence), downwards on "-" (as its reverse complement)"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        _, run_off, start, place, ln = self.thread_raw(bs)
+        out, at = [], 0
+        for i, b in enumerate(bs):
+            out.append([(start[r] - at, place[r] >> 33, (place[r] >> 1) & 0xFFFFFFFF, "-" if place[r] & 1 else "+", ln[r]) for r in range(run_off[i], run_off[i + 1])])
+            at += len(b)
+        return out
 
     def _num_unitigs(self):
         n, tb = C.c_uint64(), C.c_uint64()

@@ -39,6 +39,7 @@
 #include "k_split.h"
 #include "k_index.h"
 #include "k_quant.h"
+#include "k_thread.h"
 
 using namespace cdbg;
 
@@ -51,6 +52,7 @@ using namespace cdbg;
 #include "host_relink.h"
 #include "host_index.h"
 #include "host_quant.h"
+#include "host_thread.h"
 
 
 // =======================================================================================
@@ -280,6 +282,17 @@ int cdbg_quant_reset(cdbg_ctx* c) {
     if (!c) return fail(CDBG_E_PARAM, "null context");
     (void)hipSetDevice(c->prm.device_id);
     return quant_reset_impl(c);
+}
+// ---- run-length lookup: the walk of the caller's sequences through the resident unitigs (k_thread.h, host_thread.h) ----
+int cdbg_thread(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[4]) {
+    if (!c || !out || (n_seqs && (!offsets || !bases))) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(thread_impl, c, bases, offsets, n_seqs, out) } catch (...) { thread_forget(c); return fail(CDBG_E_NOMEM, "cdbg_thread: out of host memory"); }
+}
+int cdbg_fetch_runs(cdbg_ctx* c, uint64_t* run_off, uint64_t* start, uint64_t* place, uint32_t* len) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_runs_impl(c, run_off, start, place, len);
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");

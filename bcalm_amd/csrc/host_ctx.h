@@ -324,6 +324,10 @@ struct cdbg_ctx {
     // per position, the windows added since the counters were last clamped, and the buffers of cdbg_quantify's totals and cdbg_fetch_quant's read-out
     DBuf<uint64_t> kmer_off; DBuf<uint32_t> quant_cnt; bool quant_ready = false; uint64_t quant_tally = 0;
     DBuf<uint64_t> quant_out, quant_kc; DBuf<uint32_t> quant_cov, quant_rep;
+    // run-length lookup (host_thread.h): the totals, heads / tails per tile with their scans and one batch's runs on the device; the runs of the latest
+    // cdbg_thread on the host -- run_off[n + 1] per sequence, start / place / len per run -- until the next one or until the set is replaced
+    DBuf<uint64_t> th_out, th_hoff, th_toff, th_start, th_place, th_tail; DBuf<uint32_t> th_nh, th_nt, th_len;
+    std::vector<uint64_t> run_off, run_start, run_place; std::vector<uint32_t> run_len; bool runs_ready = false;
     DBuf<uint4> rank_a, rank_b; DBuf<uint32_t> rank_flag;
     DBuf<uint4> walk_rec; DBuf<uint32_t> walk_heads, walk_hlen; DBuf<uint64_t> walk_hoff; bool walk_off = false;   // chains walked from their heads (k_walk.h); walk_off: a run of this context had a chain the walk does not take
     // multi-GPU: transport (RCCL or caller-supplied) and the record exchange buffers

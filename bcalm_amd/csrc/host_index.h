@@ -4,10 +4,18 @@
 
 namespace {
 
+// the runs cdbg_thread keeps for cdbg_fetch_runs (host_thread.h)
+void thread_forget(cdbg_ctx* c) {
+    c->runs_ready = false;
+    std::vector<uint64_t>().swap(c->run_off); std::vector<uint64_t>().swap(c->run_start); std::vector<uint64_t>().swap(c->run_place);
+    std::vector<uint32_t>().swap(c->run_len);
+}
+
 // whatever replaces the resident set forgets its index: the table goes back to the pool
 void index_forget(cdbg_ctx* c) {
     c->indexed = false; c->index_slots.release(); c->kmer_off.release();
     c->quant_ready = false; c->quant_tally = 0; c->quant_cnt.release();      // the counters of cdbg_quantify go with the table (host_quant.h)
+    thread_forget(c);                                                        // ... and so do the runs of cdbg_thread
     for (uint64_t& v : c->index_info) v = 0;
 }
 

@@ -16,6 +16,9 @@
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -quantify sample.fq[.gz] [-all-abundance-counts] [-out prefix]
 //     reads <prefix>.unitigs.fa, counts the k-mers of the sample at the unitig positions that spell them (cdbg_load_unitigs + cdbg_quantify +
 //     cdbg_fetch_quant) and writes <prefix>.quant.tsv: unitig, k-mers, KC, covered k-mers, km [, the per-position counts].
+//   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -thread queries.fa[.gz] [-out prefix]
+//     as -query, with the runs computed on the device (cdbg_load_unitigs + cdbg_index + cdbg_thread + cdbg_fetch_runs): writes
+//     <prefix>.thread.tsv in the line format of <prefix>.query.tsv.
 // Everything between parsing and writing is three calls into libcdbg.so (include/cdbg.h):
 // this file is the replacement for bcalm_1::execute()/Functor (src/bcalm_1.cpp:49-97).
 #include <zlib.h>
@@ -57,6 +60,7 @@ struct Options {
     bool redo_links = false, skip_bcalm = false, skip_bglue = false;   // -redo-links: only the link step, on an existing <prefix>.unitigs.fa
     std::string solid_out;
     std::string quantify;                            // -quantify <file>: count the k-mers of its sequences per unitig of an existing <prefix>.unitigs.fa
+    std::string thread;                              // -thread <file>: the runs of its sequences' k-mers along the unitigs of an existing <prefix>.unitigs.fa
     std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
 
@@ -83,6 +87,7 @@ Options parse(int argc, char** argv) {
         else if (a == "-redo-links") o.redo_links = true;             // the reference's hidden option: scripts/pufferize.py:143 tells its users to run it
         else if (a == "-query") o.query = need("-query");
         else if (a == "-quantify") o.quantify = need("-quantify");
+        else if (a == "-thread") o.thread = need("-thread");
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -791,6 +796,78 @@ int query_mode(const Options& o, const std::string& prefix, int threads) {
     return EXIT_SUCCESS;
 }
 
+// ---- -thread: the walk of every query sequence through the unitigs, folded into runs on the device (cdbg_load_unitigs + cdbg_index + cdbg_thread + cdbg_fetch_runs) ----
+int thread_mode(const Options& o, const std::string& prefix, int threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = clk::now();
+    const std::string fa = prefix + ".unitigs.fa", tsv = prefix + ".thread.tsv";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-thread", F);
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F);
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    F.seq.reset(); F.slices.clear(); F.mp.reset();                 // (the set is resident: the host copy is not needed again)
+    const auto t1 = clk::now();
+    check(cdbg_index(ctx));
+    const auto t2 = clk::now();
+    // written beside the target and renamed over it: a failure leaves an earlier table as it was
+    struct TmpOut {
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+    } tmp;
+    tmp.name = tsv + ".tmp" + std::to_string((long)getpid());
+    tmp.f = fopen(tmp.name.c_str(), "w");
+    if (!tmp.f) { const std::string n = tmp.name; tmp.name.clear(); usage_error("cannot write " + n); }
+    const uint64_t BATCH = 64ull << 20, K = (uint64_t)o.k;
+    std::string bases, out; std::vector<std::string> names; std::vector<uint64_t> off{ 0 }, run_off, start, place; std::vector<uint32_t> len;
+    uint64_t n_seqs = 0, n_kmers = 0, n_found = 0, n_runs = 0, n_ext = 0; double thread_s = 0; bool wfail = false;
+    auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+    auto flush = [&]() {
+        if (names.empty()) return;
+        uint64_t tot[4];
+        const auto q0 = clk::now();
+        check(cdbg_thread(ctx, bases.data(), off.data(), names.size(), tot));
+        run_off.resize(names.size() + 1); start.resize(std::max<uint64_t>(tot[2], 1)); place.resize(start.size()); len.resize(start.size());
+        check(cdbg_fetch_runs(ctx, run_off.data(), start.data(), place.data(), len.data()));
+        thread_s += secs(q0, clk::now());
+        out.clear();
+        for (size_t i = 0; i < names.size(); ++i) {
+            const uint64_t b = off[i], n = off[i + 1] - b, nk = n >= K ? n - K + 1 : 0;
+            uint64_t found = 0;
+            for (uint64_t r = run_off[i]; r < run_off[i + 1]; ++r) found += len[r];
+            out.append(names[i]); out.push_back('\t'); put_u(out, nk); out.push_back('\t'); put_u(out, found); out.push_back('\t');
+            for (uint64_t r = run_off[i]; r < run_off[i + 1]; ++r) {
+                if (r > run_off[i]) out.push_back(',');
+                put_u(out, start[r] - b); out.push_back(':'); put_u(out, len[r]); out.push_back(':'); put_u(out, place[r] >> 33); out.push_back(':');
+                out.push_back((place[r] & 1) ? '-' : '+'); out.push_back(':'); put_u(out, (place[r] >> 1) & 0xFFFFFFFFull);
+            }
+            if (run_off[i] == run_off[i + 1]) out.push_back('*');
+            out.push_back('\n');
+            n_kmers += nk;
+        }
+        if (fwrite(out.data(), 1, out.size(), tmp.f) != out.size()) wfail = true;
+        n_seqs += names.size(); n_found += tot[1]; n_runs += tot[2]; n_ext += tot[3];
+        names.clear(); bases.clear(); off.assign(1, 0);
+    };
+    parse_queries(o.thread, bases, [&](const std::string& name) {
+        if (bases.size() > BATCH && !names.empty()) {              // this record would pass 64 MB of bases: what came before it goes first
+            const std::string last = bases.substr(off.back());
+            bases.resize(off.back());
+            flush();
+            bases = last;
+        }
+        names.push_back(name); off.push_back(bases.size());
+    });
+    flush();
+    { FILE* g = tmp.f; tmp.f = nullptr; if (fclose(g) != 0) wfail = true; }
+    if (wfail) usage_error("write error on " + tmp.name);
+    if (rename(tmp.name.c_str(), tsv.c_str()) != 0) usage_error("cannot rename " + tmp.name + " to " + tsv);
+    tmp.name.clear();
+    printf("thread: %llu sequences, %llu k-mers, %llu found, %llu runs, %llu extended (load %.2f s, index %.2f s, thread %.2f s)\n", (unsigned long long)n_seqs,
+           (unsigned long long)n_kmers, (unsigned long long)n_found, (unsigned long long)n_runs, (unsigned long long)n_ext, secs(t0, t1), secs(t1, t2), thread_s);
+    printf("runs written to %s\n", tsv.c_str());
+    return EXIT_SUCCESS;
+}
+
 // ---- -quantify: the k-mers of a sample counted per unitig (cdbg_load_unitigs + cdbg_quantify + cdbg_fetch_quant) ----
 int quantify_mode(const Options& o, const std::string& prefix, int threads) {
     using clk = std::chrono::steady_clock;
@@ -879,11 +956,13 @@ int main(int argc, char** argv) {
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
+        if (!o.thread.empty() && (!o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-thread, -query, -quantify and -redo-links are separate modes: give one of them");
+        if (!o.thread.empty() && o.n_gpus != 1) usage_error("-thread runs on one GPU: -nb-gpus must be 1");
         if (!o.quantify.empty() && (!o.query.empty() || o.redo_links)) usage_error("-quantify, -query and -redo-links are separate modes: give one of them");
         if (!o.quantify.empty() && o.n_gpus != 1) usage_error("-quantify runs on one GPU: -nb-gpus must be 1");
         if (!o.query.empty() && o.redo_links) usage_error("-query and -redo-links are two modes: give one of them");
         if (!o.query.empty() && o.n_gpus != 1) usage_error("-query runs on one GPU: -nb-gpus must be 1");
-        if (o.redo_links || !o.query.empty() || !o.quantify.empty()) {
+        if (o.redo_links || !o.query.empty() || !o.quantify.empty() || !o.thread.empty()) {
             if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
             const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
             if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
@@ -891,6 +970,7 @@ int main(int argc, char** argv) {
                 prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
             }
             int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            if (!o.thread.empty()) return thread_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.quantify.empty()) return quantify_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.query.empty()) return query_mode(o, prefix, std::max(1, std::min(threads, 60)));
             return redo_links(o, prefix, std::max(1, std::min(threads, 60)));

@@ -85,7 +85,7 @@ typedef struct cdbg_stats_t {
 /* ABI version: bumped whenever a struct of this header changes.  From version 5 on cdbg_stats_t only ever GROWS AT ITS END;
  * a binding checks cdbg_abi_version() against the header it was written for and sizeof(cdbg_stats_t) against
  * cdbg_stats_sizeof() when it loads the library (bcalm_amd/api.py does), instead of reading fields at stale offsets. */
-#define CDBG_ABI_VERSION 8
+#define CDBG_ABI_VERSION 9
 int cdbg_abi_version(void);
 uint64_t cdbg_stats_sizeof(void);
 
@@ -325,6 +325,29 @@ int cdbg_quantify(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uin
 int cdbg_fetch_quant(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint64_t* kc, uint32_t* covered, uint32_t* ab, uint64_t* ab_off);
 int cdbg_quant_reset(cdbg_ctx* ctx);
 
+/* Run-length lookup: the WALK of every sequence through the graph -- the maximal runs of consecutive k-mers that lie on one unitig, on one
+ * strand, at consecutive offsets -- computed on the device; only the runs come back (bcalm_amd/csrc/k_thread.h).  Preconditions as for
+ * cdbg_query (after cdbg_glue / cdbg_run or cdbg_load_unitigs, one rank; CDBG_E_STATE otherwise).
+ * A run is defined by the hit words cdbg_query reports, and by nothing else.  Number the positions g of the concatenated text from
+ * offsets[0], as hits[] is numbered.  Position g CONTINUES g - 1 when neither hit word is UINT64_MAX, their unitigs are equal, their
+ * strands are equal and offset(g) == offset(g - 1) + 1 on strand 0, offset(g - 1) - 1 on strand 1.  A head is a hit that does not continue
+ * its predecessor, a tail a hit whose successor does not continue it; the i-th head and the i-th tail, in position order, bound run i:
+ *   start   the head's position (relative to offsets[0], as the index into hits[])
+ *   place   the head's hit word: (unitig << 33) | (offset << 1) | strand
+ *   len     tail - head + 1 windows: unitig `unitig` spells the sequence's bases start .. start + len + k - 2 from `offset` on (strand 0),
+ *           or their reverse complement, ending at offset + k (strand 1)
+ * Sequence ends and bytes outside ACGTacgt break runs (their windows miss); a k-mer that is its own reverse complement reports strand 0
+ * and may therefore cut a strand-1 walk; in a set that repeats k-mers the runs are those of the smallest-occurrence hits.
+ * cdbg_thread (builds the index when it is not there): input as cdbg_query takes it.  out (not NULL): out[0] = valid windows, out[1] =
+ *   windows found, out[2] = runs, out[3] = windows answered from the neighbouring hit without a probe (0 in a set that repeats k-mers, and
+ *   under CDBG_QUANT_NO_EXTEND).  The hit words never leave the device; device memory per call is bounded as for cdbg_query, the result
+ *   does not depend on the batch size.  n_seqs == 0, or no bases: success, zeros and no runs.
+ * cdbg_fetch_runs: the runs of the LATEST cdbg_thread, which the library keeps in host memory until the next cdbg_thread, cdbg_reset,
+ *   cdbg_load_unitigs, cdbg_glue or cdbg_destroy (CDBG_E_STATE when there are none).  run_off[n_seqs + 1]: run_off[i] .. run_off[i + 1]
+ *   are the runs of sequence i, in position order; start, place, len: out[2] values each.  Any of the four may be NULL. */
+int cdbg_thread(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[4]);
+int cdbg_fetch_runs(cdbg_ctx* ctx, uint64_t* run_off, uint64_t* start, uint64_t* place, uint32_t* len);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
@@ -339,11 +362,11 @@ int cdbg_quant_reset(cdbg_ctx* ctx);
  *   CDBG_POISON_ALLOC=<byte>      every device block newly obtained without a request for zeroing (fresh, or from the process's pool) is
  *                                 filled with that byte (0xFF, 0xA5, ...): no kernel may depend on what a buffer held before.  Read for every
  *                                 new block, never on the path that keeps an existing allocation
- *   CDBG_QUERY_BATCH=<n>          cdbg_query: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
+ *   CDBG_QUERY_BATCH=<n>          cdbg_query, cdbg_quantify, cdbg_thread: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
  *   CDBG_INDEX_LOG2_SLOTS=<n>     cdbg_index: a table of 2^n slots, floored at the smallest power of two > distinct k-mers (and never larger
  *                                 than the default): long probe runs that wrap around the table's end
  *   CDBG_QUANT_CLAMP_WINDOWS=<n>  cdbg_quantify: clamp the counters before more than n windows (default and at most 2^31) were added since the last clamp
- *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify: every window probes the index (out[2] = 0)
+ *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify, cdbg_thread: every window probes the index (no window answered by extension)
  *   CDBG_QUANT_CEILING=<n>        cdbg_quantify / cdbg_fetch_quant: counts are exact below n (default and at most 2^31 - 4096) and reported as 2147483647
  *                                 from there on.  THE ONE HOOK THAT CHANGES REPORTED VALUES: it brings the saturation rule within reach of a test */
 
