@@ -43,13 +43,13 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-ABI_VERSION = 9                                        # include/cdbg.h CDBG_ABI_VERSION this binding was written for
+ABI_VERSION = 10                                       # include/cdbg.h CDBG_ABI_VERSION this binding was written for
 EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy", "cdbg_release_cached", "cdbg_last_error", "cdbg_push_reads", "cdbg_push_text",
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
            "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
-           "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset", "cdbg_thread", "cdbg_fetch_runs",
+           "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset", "cdbg_thread", "cdbg_fetch_runs", "cdbg_components", "cdbg_fetch_components",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -121,6 +121,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_quant_reset.argtypes = [vp]
     lib.cdbg_thread.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
     lib.cdbg_fetch_runs.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32)]
+    lib.cdbg_components.argtypes = [vp, C.POINTER(u64)]
+    lib.cdbg_fetch_components.argtypes = [vp, C.POINTER(C.c_uint32), u64, u64, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -334,6 +336,27 @@ class Graph:
             out.append([(start[r] - at, place[r] >> 33, (place[r] >> 1) & 0xFFFFFFFF, "-" if place[r] & 1 else "+", ln[r]) for r in range(run_off[i], run_off[i + 1])])
             at += len(b)
         return out
+
+    # ---- connected components of the unitig graph (cdbg_components / cdbg_fetch_components) ----
+    def components_raw(self, first=0, count=None):
+        """-> (totals, comp, first_unitig, n_unitigs, bases, kmers, kc): {components, largest, largest_id, singletons} of the resident set,
+        the component of every unitig (same order as unitigs()) and the per-component arrays of components [first, first + count) (default:
+        all) as ctypes arrays.  Components are numbered in the order of their smallest unitig.  No Python object per unitig"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.cdbg_components(self._h, out))
+        U, n = self._num_unitigs(), (out[0] - first if count is None else count)
+        comp = (C.c_uint32 * max(U, 1))()
+        fu = (C.c_uint32 * max(n, 1))()
+        nu, bases, kmers, kc = ((C.c_uint64 * max(n, 1))() for _ in range(4))
+        self._ck(self.lib.cdbg_fetch_components(self._h, comp, first, n, fu, nu, bases, kmers, kc))
+        return {"components": out[0], "largest": out[1], "largest_id": out[2], "singletons": out[3]}, comp, fu, nu, bases, kmers, kc
+
+    def components(self):
+        """-> (labels, components): the component of every unitig (same order as unitigs()), and per component
+        {first_unitig, unitigs, bases, kmers, kc}: its smallest unitig, its unitigs, the sum of their lengths, of their k-mers, of their KC"""
+        tot, comp, fu, nu, bases, kmers, kc = self.components_raw()
+        U = self._num_unitigs()
+        return list(comp[:U]), [{"first_unitig": fu[i], "unitigs": nu[i], "bases": bases[i], "kmers": kmers[i], "kc": kc[i]} for i in range(tot["components"])]
 
     def _num_unitigs(self):
         n, tb = C.c_uint64(), C.c_uint64()

@@ -40,6 +40,7 @@
 #include "k_index.h"
 #include "k_quant.h"
 #include "k_thread.h"
+#include "k_components.h"
 
 using namespace cdbg;
 
@@ -53,6 +54,7 @@ using namespace cdbg;
 #include "host_index.h"
 #include "host_quant.h"
 #include "host_thread.h"
+#include "host_components.h"
 
 
 // =======================================================================================
@@ -293,6 +295,17 @@ int cdbg_fetch_runs(cdbg_ctx* c, uint64_t* run_off, uint64_t* start, uint64_t* p
     if (!c) return fail(CDBG_E_PARAM, "null context");
     (void)hipSetDevice(c->prm.device_id);
     return fetch_runs_impl(c, run_off, start, place, len);
+}
+// ---- connected components of the unitig graph (k_components.h, host_components.h) ----
+int cdbg_components(cdbg_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    DISPATCH_WA(components_impl, c, out)
+}
+int cdbg_fetch_components(cdbg_ctx* c, uint32_t* comp, uint64_t first, uint64_t n, uint32_t* first_unitig, uint64_t* n_unitigs, uint64_t* bases, uint64_t* kmers, uint64_t* kc) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_components_impl(c, comp, first, n, first_unitig, n_unitigs, bases, kmers, kc);
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");

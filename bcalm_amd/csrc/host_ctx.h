@@ -328,6 +328,9 @@ struct cdbg_ctx {
     // cdbg_thread on the host -- run_off[n + 1] per sequence, start / place / len per run -- until the next one or until the set is replaced
     DBuf<uint64_t> th_out, th_hoff, th_toff, th_start, th_place, th_tail; DBuf<uint32_t> th_nh, th_nt, th_len;
     std::vector<uint64_t> run_off, run_start, run_place; std::vector<uint32_t> run_len; bool runs_ready = false;
+    // connected components (host_components.h): the component of every unitig and the totals per component, on the device until the set is replaced;
+    // comp_info: [0] components [1] unitigs in the largest [2] its id [3] components of one unitig [4] k-mers of the largest
+    DBuf<uint32_t> comp, comp_first; DBuf<uint64_t> comp_unitigs, comp_bases, comp_kmers, comp_kc; bool comp_ready = false; uint64_t comp_info[5] = { 0, 0, 0, 0, 0 };
     DBuf<uint4> rank_a, rank_b; DBuf<uint32_t> rank_flag;
     DBuf<uint4> walk_rec; DBuf<uint32_t> walk_heads, walk_hlen; DBuf<uint64_t> walk_hoff; bool walk_off = false;   // chains walked from their heads (k_walk.h); walk_off: a run of this context had a chain the walk does not take
     // multi-GPU: transport (RCCL or caller-supplied) and the record exchange buffers

@@ -11,11 +11,19 @@ void thread_forget(cdbg_ctx* c) {
     std::vector<uint32_t>().swap(c->run_len);
 }
 
+// the labels and totals cdbg_components keeps for cdbg_fetch_components (host_components.h)
+void components_forget(cdbg_ctx* c) {
+    c->comp_ready = false;
+    c->comp.release(); c->comp_first.release(); c->comp_unitigs.release(); c->comp_bases.release(); c->comp_kmers.release(); c->comp_kc.release();
+    for (uint64_t& v : c->comp_info) v = 0;
+}
+
 // whatever replaces the resident set forgets its index: the table goes back to the pool
 void index_forget(cdbg_ctx* c) {
     c->indexed = false; c->index_slots.release(); c->kmer_off.release();
     c->quant_ready = false; c->quant_tally = 0; c->quant_cnt.release();      // the counters of cdbg_quantify go with the table (host_quant.h)
     thread_forget(c);                                                        // ... and so do the runs of cdbg_thread
+    components_forget(c);                                                    // ... and the component labels of cdbg_components
     for (uint64_t& v : c->index_info) v = 0;
 }
 

@@ -19,6 +19,9 @@
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -thread queries.fa[.gz] [-out prefix]
 //     as -query, with the runs computed on the device (cdbg_load_unitigs + cdbg_index + cdbg_thread + cdbg_fetch_runs): writes
 //     <prefix>.thread.tsv in the line format of <prefix>.query.tsv.
+//   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -components [-out prefix]
+//     reads <prefix>.unitigs.fa, labels the connected components of its records' graph (cdbg_load_unitigs + cdbg_components +
+//     cdbg_fetch_components; links recomputed from the sequences) and writes <prefix>.components.tsv and <prefix>.unitig_components.tsv.
 // Everything between parsing and writing is three calls into libcdbg.so (include/cdbg.h):
 // this file is the replacement for bcalm_1::execute()/Functor (src/bcalm_1.cpp:49-97).
 #include <zlib.h>
@@ -61,6 +64,7 @@ struct Options {
     std::string solid_out;
     std::string quantify;                            // -quantify <file>: count the k-mers of its sequences per unitig of an existing <prefix>.unitigs.fa
     std::string thread;                              // -thread <file>: the runs of its sequences' k-mers along the unitigs of an existing <prefix>.unitigs.fa
+    bool components = false;                         // -components: the connected components of the records of an existing <prefix>.unitigs.fa
     std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
 
@@ -88,6 +92,7 @@ Options parse(int argc, char** argv) {
         else if (a == "-query") o.query = need("-query");
         else if (a == "-quantify") o.quantify = need("-quantify");
         else if (a == "-thread") o.thread = need("-thread");
+        else if (a == "-components") o.components = true;
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -562,10 +567,10 @@ void read_unitig_file(const Options& o, const std::string& fa, int threads, cons
         F.off[nu] = tb;
     }
 }
-cdbg_ctx* load_unitig_file(const Options& o, const std::string& fa, UnitigFile& F) {
+cdbg_ctx* load_unitig_file(const Options& o, const std::string& fa, UnitigFile& F, const uint64_t* kc = nullptr) {
     cdbg_params prm{}; prm.k = o.k; prm.abundance_min = std::max(1, o.amin); prm.minimizer_size = 0; prm.log2_partitions = -1; prm.device_id = o.device; prm.world_size = 1;
     cdbg_ctx* ctx = nullptr; check(cdbg_create(&prm, &ctx));
-    if (cdbg_load_unitigs(ctx, F.seq.get(), F.off.data(), F.nu, nullptr) != 0) {
+    if (cdbg_load_unitigs(ctx, F.seq.get(), F.off.data(), F.nu, kc) != 0) {
         const std::string e = cdbg_last_error(); unsigned long long u = 0;
         cdbg_destroy(ctx);
         if (sscanf(e.c_str(), "unitig %llu", &u) == 1) usage_error(fa + ": record " + std::to_string(u) + ": " + e);
@@ -868,6 +873,66 @@ int thread_mode(const Options& o, const std::string& prefix, int threads) {
     return EXIT_SUCCESS;
 }
 
+// ---- -components: the connected components of the records' graph (cdbg_load_unitigs + cdbg_components + cdbg_fetch_components) ----
+int components_mode(const Options& o, const std::string& prefix, int threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = clk::now();
+    const std::string fa = prefix + ".unitigs.fa", ctsv = prefix + ".components.tsv", utsv = prefix + ".unitig_components.tsv";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-components", F);
+    const uint64_t nu = F.nu;
+    std::vector<uint64_t> kc(nu ? nu : 1, 0);                      // the KC:i: token of every header (0 where a record has none)
+    for (uint64_t i = 0; i < nu; ++i) {
+        const std::string& r = *F.rest[i];
+        for (size_t p = 0; p < r.size();) {
+            size_t q = r.find(' ', p); if (q == std::string::npos) q = r.size();
+            if (r.compare(p, 5, "KC:i:") == 0) { kc[i] = strtoull(r.c_str() + p + 5, nullptr, 10); break; }
+            p = q + 1;
+        }
+    }
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F, kc.data());
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    F.seq.reset(); F.slices.clear(); F.mp.reset();                 // (the set is resident: the host copy is not needed again)
+    const auto t1 = clk::now();
+    uint64_t tot[4]; check(cdbg_components(ctx, tot));
+    const uint64_t nc = tot[0];
+    std::vector<uint32_t> comp(nu ? nu : 1), first(nc ? nc : 1); std::vector<uint64_t> n_un(nc ? nc : 1), bases(n_un.size()), kmers(n_un.size()), ckc(n_un.size());
+    check(cdbg_fetch_components(ctx, comp.data(), 0, nc, first.data(), n_un.data(), bases.data(), kmers.data(), ckc.data()));
+    const auto t2 = clk::now();
+    // both tables are written beside their targets and renamed over them: a failure leaves earlier tables as they were
+    struct TmpOut {
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+        void open(const std::string& n) { f = fopen(n.c_str(), "w"); if (!f) usage_error("cannot write " + n); name = n; }
+        bool close() { FILE* g = f; f = nullptr; return !g || fclose(g) == 0; }
+        bool commit(const std::string& to) { if (rename(name.c_str(), to.c_str()) != 0) return false; name.clear(); return true; }
+    } tc, tu;
+    tc.open(ctsv + ".tmp" + std::to_string((long)getpid())); tu.open(utsv + ".tmp" + std::to_string((long)getpid()));
+    auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+    bool wfail = false; std::string out;
+    auto flush = [&](FILE* f, bool all) { if (all || out.size() > (1u << 20)) { if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size()) wfail = true; out.clear(); } };
+    out = "#component\tunitigs\tbases\tkmers\tKC\tfirst_unitig\n";
+    for (uint64_t c = 0; c < nc; ++c) {
+        put_u(out, c); out.push_back('\t'); put_u(out, n_un[c]); out.push_back('\t'); put_u(out, bases[c]); out.push_back('\t'); put_u(out, kmers[c]); out.push_back('\t');
+        put_u(out, ckc[c]); out.push_back('\t'); put_u(out, first[c]); out.push_back('\n');
+        flush(tc.f, false);
+    }
+    flush(tc.f, true);
+    out = "#unitig\tcomponent\n";
+    for (uint64_t u = 0; u < nu; ++u) { put_u(out, u); out.push_back('\t'); put_u(out, comp[u]); out.push_back('\n'); flush(tu.f, false); }
+    flush(tu.f, true);
+    if (!tc.close()) wfail = true;
+    if (!tu.close()) wfail = true;
+    if (wfail) usage_error("write error on " + tc.name + " / " + tu.name);
+    if (!tc.commit(ctsv)) usage_error("cannot rename " + tc.name + " to " + ctsv);
+    if (!tu.commit(utsv)) usage_error("cannot rename " + tu.name + " to " + utsv);
+    if (o.verbose) printf("components: %llu components, %llu unitigs in the largest (component %llu), %llu components of one unitig\n", (unsigned long long)tot[0],
+                          (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3]);
+    printf("components: %llu unitigs in %llu components (load %.2f s, components %.2f s)\n", (unsigned long long)nu, (unsigned long long)nc, secs(t0, t1), secs(t1, t2));
+    printf("components written to %s and %s\n", ctsv.c_str(), utsv.c_str());
+    return EXIT_SUCCESS;
+}
+
 // ---- -quantify: the k-mers of a sample counted per unitig (cdbg_load_unitigs + cdbg_quantify + cdbg_fetch_quant) ----
 int quantify_mode(const Options& o, const std::string& prefix, int threads) {
     using clk = std::chrono::steady_clock;
@@ -956,13 +1021,15 @@ int main(int argc, char** argv) {
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
+        if (o.components && (!o.thread.empty() || !o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-components, -thread, -query, -quantify and -redo-links are separate modes: give one of them");
+        if (o.components && o.n_gpus != 1) usage_error("-components runs on one GPU: -nb-gpus must be 1");
         if (!o.thread.empty() && (!o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-thread, -query, -quantify and -redo-links are separate modes: give one of them");
         if (!o.thread.empty() && o.n_gpus != 1) usage_error("-thread runs on one GPU: -nb-gpus must be 1");
         if (!o.quantify.empty() && (!o.query.empty() || o.redo_links)) usage_error("-quantify, -query and -redo-links are separate modes: give one of them");
         if (!o.quantify.empty() && o.n_gpus != 1) usage_error("-quantify runs on one GPU: -nb-gpus must be 1");
         if (!o.query.empty() && o.redo_links) usage_error("-query and -redo-links are two modes: give one of them");
         if (!o.query.empty() && o.n_gpus != 1) usage_error("-query runs on one GPU: -nb-gpus must be 1");
-        if (o.redo_links || !o.query.empty() || !o.quantify.empty() || !o.thread.empty()) {
+        if (o.redo_links || !o.query.empty() || !o.quantify.empty() || !o.thread.empty() || o.components) {
             if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
             const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
             if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
@@ -970,6 +1037,7 @@ int main(int argc, char** argv) {
                 prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
             }
             int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            if (o.components) return components_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.thread.empty()) return thread_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.quantify.empty()) return quantify_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.query.empty()) return query_mode(o, prefix, std::max(1, std::min(threads, 60)));

@@ -85,7 +85,7 @@ typedef struct cdbg_stats_t {
 /* ABI version: bumped whenever a struct of this header changes.  From version 5 on cdbg_stats_t only ever GROWS AT ITS END;
  * a binding checks cdbg_abi_version() against the header it was written for and sizeof(cdbg_stats_t) against
  * cdbg_stats_sizeof() when it loads the library (bcalm_amd/api.py does), instead of reading fields at stale offsets. */
-#define CDBG_ABI_VERSION 9
+#define CDBG_ABI_VERSION 10
 int cdbg_abi_version(void);
 uint64_t cdbg_stats_sizeof(void);
 
@@ -347,6 +347,25 @@ int cdbg_quant_reset(cdbg_ctx* ctx);
  *   are the runs of sequence i, in position order; start, place, len: out[2] values each.  Any of the four may be NULL. */
 int cdbg_thread(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[4]);
 int cdbg_fetch_runs(cdbg_ctx* ctx, uint64_t* run_off, uint64_t* start, uint64_t* place, uint32_t* len);
+
+/* Connected components of the unitig graph: which unitigs hang together, how many pieces there are, how big each one is
+ * (bcalm_amd/csrc/k_components.h).  Two unitigs share a component exactly when a path of links joins them; sign and direction of the links
+ * are ignored, and a unitig whose only links lead to itself is a component of one.  Read-only: nothing that is resident changes.
+ * Preconditions as for cdbg_query (after cdbg_glue / cdbg_run or cdbg_load_unitigs, one rank; CDBG_E_STATE otherwise).
+ * cdbg_components (builds the links when they are not there, as cdbg_verify does): out (not NULL): out[0] = components, out[1] = unitigs
+ *   in the largest component, out[2] = the id of that component (the smallest id on a tie), out[3] = components of exactly one unitig.  An
+ *   empty set gives zeros.  Components are numbered 0 .. out[0] - 1 in the order of their smallest unitig: the labels and totals are the
+ *   same bytes on every run.  Device memory: 16 bytes per unitig while the call runs, of which the 4 bytes of the label stay, and 36 bytes
+ *   per component; what does not fit is CDBG_E_NOMEM with the sizes in the message.
+ * cdbg_fetch_components: the result of the LATEST cdbg_components, which the library keeps on the device until cdbg_reset,
+ *   cdbg_load_unitigs, cdbg_glue or cdbg_destroy (CDBG_E_STATE when there is none; a repeated cdbg_link does not invalidate it).
+ *   comp[n_unitigs] (or NULL): the component of every unitig, in the order of cdbg_fetch_unitigs.  The per-component arrays (n values
+ *   each, any may be NULL) cover the components [first, first + n), a range outside [0, out[0]] is CDBG_E_PARAM: first_unitig = the
+ *   smallest unitig of the component (strictly ascending), n_unitigs, bases = the sum of the unitigs' lengths, kmers = the sum of
+ *   LN - k + 1, kc = the sum of KC. */
+int cdbg_components(cdbg_ctx* ctx, uint64_t out[4]);
+int cdbg_fetch_components(cdbg_ctx* ctx, uint32_t* comp, uint64_t first, uint64_t n, uint32_t* first_unitig, uint64_t* n_unitigs, uint64_t* bases,
+                          uint64_t* kmers, uint64_t* kc);
 
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
