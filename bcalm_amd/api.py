@@ -43,13 +43,14 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-ABI_VERSION = 10                                       # include/cdbg.h CDBG_ABI_VERSION this binding was written for
+ABI_VERSION = 11                                       # include/cdbg.h CDBG_ABI_VERSION this binding was written for
 EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy", "cdbg_release_cached", "cdbg_last_error", "cdbg_push_reads", "cdbg_push_text",
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
            "cdbg_verify_edges", "cdbg_verify_unitigs",
            "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
            "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset", "cdbg_thread", "cdbg_fetch_runs", "cdbg_components", "cdbg_fetch_components",
+           "cdbg_color_open", "cdbg_color", "cdbg_color_classes", "cdbg_fetch_color_runs", "cdbg_fetch_color_classes",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -123,6 +124,12 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_fetch_runs.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.cdbg_components.argtypes = [vp, C.POINTER(u64)]
     lib.cdbg_fetch_components.argtypes = [vp, C.POINTER(C.c_uint32), u64, u64, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    u32 = C.c_uint32
+    lib.cdbg_color_open.argtypes = [vp, u32]
+    lib.cdbg_color.argtypes = [vp, u32, C.c_char_p, C.POINTER(u64), u64, C.POINTER(u64)]
+    lib.cdbg_color_classes.argtypes = [vp, C.POINTER(u64)]
+    lib.cdbg_fetch_color_runs.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    lib.cdbg_fetch_color_classes.argtypes = [vp, u64, u64, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -144,6 +151,7 @@ class Graph:
         p = Params(k, abundance_min, minimizer_size, log2_partitions, device_id, world_size, rank, 1 if all_abundance_counts else 0,
                    1 if emit_replicated else 0, 1 if reads_replicated else 0)
         self._h = C.c_void_p()
+        self._color = None                                   # (colours opened, totals of cdbg_color_classes or None): see _color_forget()
         self._ck(self.lib.cdbg_create(C.byref(p), C.byref(self._h)))
 
     def _ck(self, rc):
@@ -220,6 +228,7 @@ class Graph:
             if len(kc) != len(bs):
                 raise ValueError("kc: one value per sequence")
             kcs = (C.c_uint64 * max(len(bs), 1))(*[int(x) for x in kc])
+        self._color_forget()
         self._ck(self.lib.cdbg_load_unitigs(self._h, b"".join(bytes(b) for b in bs), off, len(bs), kcs))
 
     # ---- node lookup (cdbg_index / cdbg_query) ----
@@ -358,6 +367,75 @@ class Graph:
         U = self._num_unitigs()
         return list(comp[:U]), [{"first_unitig": fu[i], "unitigs": nu[i], "bases": bases[i], "kmers": kmers[i], "kc": kc[i]} for i in range(tot["components"])]
 
+    # ---- the resident unitigs coloured by sample (cdbg_color_open / cdbg_color / cdbg_color_classes / the two fetches) ----
+    def _color_forget(self):
+        """what this object remembers of the library's colours; with every call after which the library has none (reset, run, glue, load)"""
+        self._color = None
+
+    def color_open(self, n):
+        """n bit planes, one per sample, all empty; earlier colours and classes are forgotten"""
+        self._color_forget()
+        self._ck(self.lib.cdbg_color_open(self._h, n))
+        self._color = (n, None)
+
+    def color(self, color, seqs, first_offset=0) -> dict:
+        """mark colour `color` at the positions of the resident unitigs that spell the k-mers of `seqs` (str / bytes; any bytes, any
+        lengths); marks ACCUMULATE over calls and are idempotent.  -> {windows, found, extended} of this call, as quantify() reports them"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = first_offset
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        out = (C.c_uint64 * 3)()
+        if self._color:
+            self._color = (self._color[0], None)             # (the library forgets its classes with every further mark)
+        self._ck(self.lib.cdbg_color(self._h, color, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), out))
+        return {"windows": out[0], "found": out[1], "extended": out[2]}
+
+    def _color_totals(self):
+        """cdbg_color_classes, once per marked state: -> (colours, (runs, classes, colored, single_run_unitigs)); the fetches below share it"""
+        if not self._color or self._color[1] is None:
+            out = (C.c_uint64 * 4)()
+            self._ck(self.lib.cdbg_color_classes(self._h, out))      # (refuses where there is nothing to fold, an open included)
+            if not self._color:
+                raise CdbgError(-4, "colours were not opened through this Graph: color_open() first")
+            self._color = (self._color[0], tuple(out))
+        return self._color
+
+    def color_runs_raw(self):
+        """-> (totals, run_off, offset, len, cls): {runs, classes, colored, single_run_unitigs} and the runs as ctypes arrays -- run_off[U + 1]
+        per unitig, and per run its offset in the unitig, its length in k-mer positions and its class.  No Python object per run"""
+        _, out = self._color_totals()
+        U, R = self._num_unitigs(), out[0]
+        run_off = (C.c_uint64 * (U + 1))()
+        offset, ln, cls = ((C.c_uint32 * max(R, 1))() for _ in range(3))
+        self._ck(self.lib.cdbg_fetch_color_runs(self._h, run_off, offset, ln, cls))
+        return {"runs": R, "classes": out[1], "colored": out[2], "single_run_unitigs": out[3]}, run_off, offset, ln, cls
+
+    def color_runs(self):
+        """-> per unitig (same order as unitigs()) the list of its runs (offset, len, class): maximal intervals of k-mer positions with
+        equal colour sets; they partition the unitig's positions"""
+        _, run_off, offset, ln, cls = self.color_runs_raw()
+        return [[(offset[r], ln[r], cls[r]) for r in range(run_off[u], run_off[u + 1])] for u in range(len(run_off) - 1)]
+
+    def color_classes_raw(self, first=0, count=None):
+        """-> (n, n_colors, runs, kmers, bits, words per class): the n classes [first, first + count) (default: all) as ctypes arrays; colour c
+        of class i is bit c & 31 of bits[i * words + (c >> 5)]"""
+        n_colors, out = self._color_totals()
+        n = out[1] - first if count is None else count
+        nw = (n_colors + 31) // 32
+        ncol, bits = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n * nw, 1))()
+        runs, kmers = (C.c_uint64 * max(n, 1))(), (C.c_uint64 * max(n, 1))()
+        self._ck(self.lib.cdbg_fetch_color_classes(self._h, first, n, ncol, runs, kmers, bits))
+        return n, ncol, runs, kmers, bits, nw
+
+    def color_classes(self):
+        """-> per class, in the order of its first run, {"colors": [colour indices], "runs": runs that have it, "kmers": positions they cover}"""
+        n, ncol, runs, kmers, bits, nw = self.color_classes_raw()
+        return [{"colors": [32 * j + b for j in range(nw) for b in range(32) if (bits[i * nw + j] >> b) & 1], "runs": runs[i], "kmers": kmers[i]} for i in range(n)]
+
     def _num_unitigs(self):
         n, tb = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.cdbg_num_unitigs(self._h, C.byref(n), C.byref(tb)))
@@ -380,12 +458,15 @@ class Graph:
         self._ck(self.lib.cdbg_compact(self._h))
 
     def glue(self):
+        self._color_forget()
         self._ck(self.lib.cdbg_glue(self._h))
 
     def run(self):
+        self._color_forget()
         self._ck(self.lib.cdbg_run(self._h))
 
     def reset(self):
+        self._color_forget()
         self._ck(self.lib.cdbg_reset(self._h))
 
     def unitigs_packed(self):

@@ -41,6 +41,7 @@
 #include "k_quant.h"
 #include "k_thread.h"
 #include "k_components.h"
+#include "k_color.h"
 
 using namespace cdbg;
 
@@ -55,6 +56,7 @@ using namespace cdbg;
 #include "host_quant.h"
 #include "host_thread.h"
 #include "host_components.h"
+#include "host_color.h"
 
 
 // =======================================================================================
@@ -306,6 +308,32 @@ int cdbg_fetch_components(cdbg_ctx* c, uint32_t* comp, uint64_t first, uint64_t 
     if (!c) return fail(CDBG_E_PARAM, "null context");
     (void)hipSetDevice(c->prm.device_id);
     return fetch_components_impl(c, comp, first, n, first_unitig, n_unitigs, bases, kmers, kc);
+}
+// ---- the resident unitigs coloured by sample (k_color.h, host_color.h) ----
+int cdbg_color_open(cdbg_ctx* c, uint32_t n_colors) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(color_open_impl, c, n_colors) } catch (...) { color_forget(c); return fail(CDBG_E_NOMEM, "cdbg_color_open: out of host memory"); }
+}
+int cdbg_color(cdbg_ctx* c, uint32_t color, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[3]) {
+    if (!c || !out || (n_seqs && (!offsets || !bases))) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(color_impl, c, color, bases, offsets, n_seqs, out) } catch (...) { return fail(CDBG_E_NOMEM, "cdbg_color: out of host memory"); }
+}
+int cdbg_color_classes(cdbg_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    return color_classes_impl(c, out);
+}
+int cdbg_fetch_color_runs(cdbg_ctx* c, uint64_t* run_off, uint32_t* offset, uint32_t* len, uint32_t* cls) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_color_runs_impl(c, run_off, offset, len, cls);
+}
+int cdbg_fetch_color_classes(cdbg_ctx* c, uint64_t first, uint64_t n, uint32_t* n_colors, uint64_t* runs, uint64_t* kmers, uint32_t* bits) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_color_classes_impl(c, first, n, n_colors, runs, kmers, bits);
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");

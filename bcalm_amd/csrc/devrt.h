@@ -67,6 +67,14 @@ CDBG_DEV uint32_t atomic_cas_u32(uint32_t* p, uint32_t cmp, uint32_t v) { return
 CDBG_DEV uint32_t atomic_max_u32(uint32_t* p, uint32_t v) { return atomicMax(p, v); }
 CDBG_DEV uint32_t atomic_min_u32(uint32_t* p, uint32_t v) { return atomicMin(p, v); }
 CDBG_DEV void atomic_or_u64(uint64_t* p, uint64_t v) { (void)atomicOr((unsigned long long*)p, (unsigned long long)v); }
+// bits set in a word; the index of its lowest set bit (v != 0)
+#ifdef CDBG_HOSTSIM
+CDBG_DEV uint32_t popc_u32(uint32_t v) { return (uint32_t)__builtin_popcount(v); }
+CDBG_DEV uint32_t ctz_u32(uint32_t v) { return (uint32_t)__builtin_ctz(v); }
+#else
+CDBG_DEV uint32_t popc_u32(uint32_t v) { return (uint32_t)__popc(v); }
+CDBG_DEV uint32_t ctz_u32(uint32_t v) { return (uint32_t)(__ffs((int)v) - 1); }
+#endif
 // unaligned global accesses (gfx950 global_load/store take any byte address; one request instead of 8 / 4 / 2)
 CDBG_DEV uint64_t ld_unaligned_u64(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 CDBG_DEV void st_unaligned_u64(uint8_t* p, uint64_t v) { __builtin_memcpy(p, &v, 8); }

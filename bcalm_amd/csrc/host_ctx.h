@@ -331,6 +331,12 @@ struct cdbg_ctx {
     // connected components (host_components.h): the component of every unitig and the totals per component, on the device until the set is replaced;
     // comp_info: [0] components [1] unitigs in the largest [2] its id [3] components of one unitig [4] k-mers of the largest
     DBuf<uint32_t> comp, comp_first; DBuf<uint64_t> comp_unitigs, comp_bases, comp_kmers, comp_kc; bool comp_ready = false; uint64_t comp_info[5] = { 0, 0, 0, 0, 0 };
+    // colours (host_color.h): color_n bit planes of color_words words each (colour-major) and the plane of unitig starts, beside the index from
+    // cdbg_color_open on; the result of the latest cdbg_color_classes on the device -- run_off[U + 1], offset / len / class per run, colours / runs /
+    // k-mers / bit row per class -- until the next cdbg_color or until the set is replaced; color_info: [0] runs [1] classes [2] coloured positions
+    // [3] unitigs that are one run
+    DBuf<uint32_t> color_planes, color_ustart; uint32_t color_n = 0; uint64_t color_words = 0; bool color_opened = false; DBuf<uint64_t> color_out;
+    DBuf<uint64_t> cl_run_off, cl_runs, cl_kmers; DBuf<uint32_t> cl_offset, cl_len, cl_cls, cl_ncol, cl_bits; bool cl_ready = false; uint64_t color_info[4] = { 0, 0, 0, 0 };
     DBuf<uint4> rank_a, rank_b; DBuf<uint32_t> rank_flag;
     DBuf<uint4> walk_rec; DBuf<uint32_t> walk_heads, walk_hlen; DBuf<uint64_t> walk_hoff; bool walk_off = false;   // chains walked from their heads (k_walk.h); walk_off: a run of this context had a chain the walk does not take
     // multi-GPU: transport (RCCL or caller-supplied) and the record exchange buffers

@@ -18,12 +18,25 @@ void components_forget(cdbg_ctx* c) {
     for (uint64_t& v : c->comp_info) v = 0;
 }
 
+// the runs and classes cdbg_color_classes keeps for the two colour fetches, and the planes of cdbg_color_open (host_color.h)
+void color_classes_forget(cdbg_ctx* c) {
+    c->cl_ready = false;
+    c->cl_run_off.release(); c->cl_runs.release(); c->cl_kmers.release(); c->cl_offset.release(); c->cl_len.release(); c->cl_cls.release();
+    c->cl_ncol.release(); c->cl_bits.release();
+    for (uint64_t& v : c->color_info) v = 0;
+}
+void color_forget(cdbg_ctx* c) {
+    color_classes_forget(c);
+    c->color_opened = false; c->color_n = 0; c->color_words = 0; c->color_planes.release(); c->color_ustart.release();
+}
+
 // whatever replaces the resident set forgets its index: the table goes back to the pool
 void index_forget(cdbg_ctx* c) {
     c->indexed = false; c->index_slots.release(); c->kmer_off.release();
     c->quant_ready = false; c->quant_tally = 0; c->quant_cnt.release();      // the counters of cdbg_quantify go with the table (host_quant.h)
     thread_forget(c);                                                        // ... and so do the runs of cdbg_thread
     components_forget(c);                                                    // ... and the component labels of cdbg_components
+    color_forget(c);                                                         // ... and the colour planes, runs and classes
     for (uint64_t& v : c->index_info) v = 0;
 }
 

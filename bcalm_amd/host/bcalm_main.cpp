@@ -19,6 +19,10 @@
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -thread queries.fa[.gz] [-out prefix]
 //     as -query, with the runs computed on the device (cdbg_load_unitigs + cdbg_index + cdbg_thread + cdbg_fetch_runs): writes
 //     <prefix>.thread.tsv in the line format of <prefix>.query.tsv.
+//   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -colors samples.txt [-out prefix]
+//     reads <prefix>.unitigs.fa and the sample files samples.txt names, one per non-empty line (line i is colour i; FASTA / FASTQ, plain or
+//     gzip), marks every sample's k-mers at the unitig positions that spell them (cdbg_load_unitigs + cdbg_color_open + cdbg_color +
+//     cdbg_color_classes) and writes <prefix>.colors.tsv (unitig, offset, len, class per run) and <prefix>.color_classes.tsv.
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -components [-out prefix]
 //     reads <prefix>.unitigs.fa, labels the connected components of its records' graph (cdbg_load_unitigs + cdbg_components +
 //     cdbg_fetch_components; links recomputed from the sequences) and writes <prefix>.components.tsv and <prefix>.unitig_components.tsv.
@@ -43,6 +47,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <fstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -64,6 +69,7 @@ struct Options {
     std::string solid_out;
     std::string quantify;                            // -quantify <file>: count the k-mers of its sequences per unitig of an existing <prefix>.unitigs.fa
     std::string thread;                              // -thread <file>: the runs of its sequences' k-mers along the unitigs of an existing <prefix>.unitigs.fa
+    std::string colors;                              // -colors <list>: one sample file per line; colour the unitigs of an existing <prefix>.unitigs.fa by sample
     bool components = false;                         // -components: the connected components of the records of an existing <prefix>.unitigs.fa
     std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
@@ -93,6 +99,7 @@ Options parse(int argc, char** argv) {
         else if (a == "-quantify") o.quantify = need("-quantify");
         else if (a == "-thread") o.thread = need("-thread");
         else if (a == "-components") o.components = true;
+        else if (a == "-colors") o.colors = need("-colors");
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -933,6 +940,105 @@ int components_mode(const Options& o, const std::string& prefix, int threads) {
     return EXIT_SUCCESS;
 }
 
+// ---- -colors: the unitigs coloured by sample (cdbg_load_unitigs + cdbg_color_open + cdbg_color per sample + cdbg_color_classes + the two fetches) ----
+int colors_mode(const Options& o, const std::string& prefix, int threads) {
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t0 = clk::now();
+    // the list first: line i names the sample of colour i (empty lines are skipped); every sample must be readable before anything is loaded
+    std::vector<std::string> samples;
+    {
+        std::ifstream lf(o.colors);
+        if (!lf) usage_error("cannot open sample list " + o.colors);
+        std::string line;
+        while (std::getline(lf, line)) {
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+            if (!line.empty()) samples.push_back(line);
+        }
+    }
+    if (samples.empty()) usage_error("-colors: no samples in " + o.colors);
+    if (samples.size() > CDBG_MAX_COLORS) usage_error("-colors: " + std::to_string(samples.size()) + " samples in " + o.colors + ", at most " + std::to_string(CDBG_MAX_COLORS) + " (CDBG_MAX_COLORS)");
+    for (const std::string& sf : samples) { FILE* f = fopen(sf.c_str(), "rb"); if (!f) usage_error("cannot open sample file " + sf); fclose(f); }
+    const std::string fa = prefix + ".unitigs.fa", rtsv = prefix + ".colors.tsv", ctsv = prefix + ".color_classes.tsv";
+    UnitigFile F; read_unitig_file(o, fa, threads, "-colors", F);
+    cdbg_ctx* ctx = load_unitig_file(o, fa, F);
+    struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
+    const uint64_t nu = F.nu;
+    F.seq.reset(); F.slices.clear(); F.mp.reset();                 // (the set is resident: the host copy is not needed again)
+    const auto t1 = clk::now();
+    const uint32_t N = (uint32_t)samples.size();
+    check(cdbg_color_open(ctx, N));
+    const auto t2 = clk::now();
+    const uint64_t BATCH = 64ull << 20;
+    uint64_t tot[3] = { 0, 0, 0 };
+    for (uint32_t col = 0; col < N; ++col) {
+        std::string bases; std::vector<uint64_t> off{ 0 };
+        auto flush = [&]() {
+            if (off.size() == 1) return;
+            uint64_t out[3];
+            check(cdbg_color(ctx, col, bases.data(), off.data(), off.size() - 1, out));
+            for (int i = 0; i < 3; ++i) tot[i] += out[i];
+            bases.clear(); off.assign(1, 0);
+        };
+        parse_queries(samples[col], bases, [&](const std::string&) {
+            if (bases.size() > BATCH && off.size() > 1) {              // this record would pass 64 MB of bases: what came before it goes first
+                const std::string last = bases.substr(off.back());
+                bases.resize(off.back());
+                flush();
+                bases = last;
+            }
+            off.push_back(bases.size());
+        }, "sample file");
+        flush();
+    }
+    const auto t3 = clk::now();
+    uint64_t info[4]; check(cdbg_color_classes(ctx, info));
+    const uint64_t R = info[0], NC = info[1], NW = (N + 31) / 32;
+    std::vector<uint64_t> run_off(nu + 1), c_runs(NC ? NC : 1), c_kmers(NC ? NC : 1);
+    std::vector<uint32_t> r_off(R ? R : 1), r_len(R ? R : 1), r_cls(R ? R : 1), c_ncol(NC ? NC : 1), c_bits(NC ? NC * NW : 1);
+    check(cdbg_fetch_color_runs(ctx, run_off.data(), r_off.data(), r_len.data(), r_cls.data()));
+    check(cdbg_fetch_color_classes(ctx, 0, NC, c_ncol.data(), c_runs.data(), c_kmers.data(), c_bits.data()));
+    const auto t4 = clk::now();
+    // both tables are written beside their targets and renamed over them: a failure leaves earlier tables as they were
+    struct TmpOut {
+        std::string name; FILE* f = nullptr;
+        ~TmpOut() { if (f) fclose(f); if (!name.empty()) remove(name.c_str()); }
+        void open(const std::string& n) { f = fopen(n.c_str(), "w"); if (!f) usage_error("cannot write " + n); name = n; }
+        bool close() { FILE* g = f; f = nullptr; return !g || fclose(g) == 0; }
+        bool commit(const std::string& to) { if (rename(name.c_str(), to.c_str()) != 0) return false; name.clear(); return true; }
+    } tr, tc;
+    tr.open(rtsv + ".tmp" + std::to_string((long)getpid())); tc.open(ctsv + ".tmp" + std::to_string((long)getpid()));
+    auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
+    bool wfail = false; std::string out;
+    auto flush_out = [&](FILE* f, bool all) { if (all || out.size() > (1u << 20)) { if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size()) wfail = true; out.clear(); } };
+    for (uint64_t u = 0; u < nu; ++u)
+        for (uint64_t r = run_off[u]; r < run_off[u + 1]; ++r) {
+            put_u(out, u); out.push_back('\t'); put_u(out, r_off[r]); out.push_back('\t'); put_u(out, r_len[r]); out.push_back('\t'); put_u(out, r_cls[r]); out.push_back('\n');
+            flush_out(tr.f, false);
+        }
+    flush_out(tr.f, true);
+    for (uint64_t c = 0; c < NC; ++c) {
+        put_u(out, c); out.push_back('\t'); put_u(out, c_ncol[c]); out.push_back('\t'); put_u(out, c_runs[c]); out.push_back('\t'); put_u(out, c_kmers[c]); out.push_back('\t');
+        bool first = true;
+        for (uint32_t col = 0; col < N; ++col)
+            if ((c_bits[c * NW + (col >> 5)] >> (col & 31)) & 1u) { if (!first) out.push_back(','); put_u(out, col); first = false; }
+        if (first) out.push_back('-');
+        out.push_back('\n');
+        flush_out(tc.f, false);
+    }
+    flush_out(tc.f, true);
+    if (!tr.close()) wfail = true;
+    if (!tc.close()) wfail = true;
+    if (wfail) usage_error("write error on " + tr.name + " / " + tc.name);
+    if (!tr.commit(rtsv)) usage_error("cannot rename " + tr.name + " to " + rtsv);
+    if (!tc.commit(ctsv)) usage_error("cannot rename " + tc.name + " to " + ctsv);
+    if (o.verbose) printf("colors: %llu positions with a colour, %llu unitigs that are one run, %llu k-mers extended\n", (unsigned long long)info[2], (unsigned long long)info[3], (unsigned long long)tot[2]);
+    printf("colors: %u samples, %llu k-mers, %llu found, %llu runs, %llu classes (load %.2f s, index %.2f s, mark %.2f s, classes %.2f s)\n", N, (unsigned long long)tot[0],
+           (unsigned long long)tot[1], (unsigned long long)R, (unsigned long long)NC, secs(t0, t1), secs(t1, t2), secs(t2, t3), secs(t3, t4));
+    printf("colours written to %s and %s\n", rtsv.c_str(), ctsv.c_str());
+    return EXIT_SUCCESS;
+}
+
 // ---- -quantify: the k-mers of a sample counted per unitig (cdbg_load_unitigs + cdbg_quantify + cdbg_fetch_quant) ----
 int quantify_mode(const Options& o, const std::string& prefix, int threads) {
     using clk = std::chrono::steady_clock;
@@ -1021,6 +1127,8 @@ int main(int argc, char** argv) {
         if (o.in.empty()) usage_error("Specifiy -in");             // sic: the reference's message (bcalm_1.cpp:61)
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
+        if (!o.colors.empty() && (o.components || !o.thread.empty() || !o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-colors, -components, -thread, -query, -quantify and -redo-links are separate modes: give one of them");
+        if (!o.colors.empty() && o.n_gpus != 1) usage_error("-colors runs on one GPU: -nb-gpus must be 1");
         if (o.components && (!o.thread.empty() || !o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-components, -thread, -query, -quantify and -redo-links are separate modes: give one of them");
         if (o.components && o.n_gpus != 1) usage_error("-components runs on one GPU: -nb-gpus must be 1");
         if (!o.thread.empty() && (!o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-thread, -query, -quantify and -redo-links are separate modes: give one of them");
@@ -1029,7 +1137,7 @@ int main(int argc, char** argv) {
         if (!o.quantify.empty() && o.n_gpus != 1) usage_error("-quantify runs on one GPU: -nb-gpus must be 1");
         if (!o.query.empty() && o.redo_links) usage_error("-query and -redo-links are two modes: give one of them");
         if (!o.query.empty() && o.n_gpus != 1) usage_error("-query runs on one GPU: -nb-gpus must be 1");
-        if (o.redo_links || !o.query.empty() || !o.quantify.empty() || !o.thread.empty() || o.components) {
+        if (o.redo_links || !o.query.empty() || !o.quantify.empty() || !o.thread.empty() || o.components || !o.colors.empty()) {
             if (o.n_gpus != 1) usage_error("-redo-links runs on one GPU: -nb-gpus must be 1");
             const std::string suffix = ".unitigs.fa";                // -in may name the unitigs file itself, or the input (even the deleted .h5) of the run that wrote it
             if (o.out.empty() && o.in.size() > suffix.size() && o.in.compare(o.in.size() - suffix.size(), suffix.size(), suffix) == 0) {
@@ -1037,6 +1145,7 @@ int main(int argc, char** argv) {
                 prefix = o.in.substr(sl == std::string::npos ? 0 : sl + 1); prefix.resize(prefix.size() - suffix.size());
             }
             int threads = o.cores > 0 ? o.cores : (int)std::min<unsigned>(usable_cpus(), 32u);
+            if (!o.colors.empty()) return colors_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (o.components) return components_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.thread.empty()) return thread_mode(o, prefix, std::max(1, std::min(threads, 60)));
             if (!o.quantify.empty()) return quantify_mode(o, prefix, std::max(1, std::min(threads, 60)));

@@ -85,7 +85,7 @@ typedef struct cdbg_stats_t {
 /* ABI version: bumped whenever a struct of this header changes.  From version 5 on cdbg_stats_t only ever GROWS AT ITS END;
  * a binding checks cdbg_abi_version() against the header it was written for and sizeof(cdbg_stats_t) against
  * cdbg_stats_sizeof() when it loads the library (bcalm_amd/api.py does), instead of reading fields at stale offsets. */
-#define CDBG_ABI_VERSION 10
+#define CDBG_ABI_VERSION 11
 int cdbg_abi_version(void);
 uint64_t cdbg_stats_sizeof(void);
 
@@ -367,6 +367,39 @@ int cdbg_components(cdbg_ctx* ctx, uint64_t out[4]);
 int cdbg_fetch_components(cdbg_ctx* ctx, uint32_t* comp, uint64_t first, uint64_t n, uint32_t* first_unitig, uint64_t* n_unitigs, uint64_t* bases,
                           uint64_t* kmers, uint64_t* kc);
 
+/* Colours: which of N samples hold the k-mer at every position of every resident unitig, where along a unitig that answer changes, and
+ * how many distinct sample sets there are (bcalm_amd/csrc/k_color.h).  Preconditions as for cdbg_query (after cdbg_glue / cdbg_run or
+ * cdbg_load_unitigs, one rank; CDBG_E_STATE otherwise).  Positions are numbered g = kmer_off[u] + offset, as cdbg_fetch_quant lays its
+ * counts out.  The library keeps N planes of one bit per position (N x P / 8 bytes beside the index, against 4 x P for one set of
+ * cdbg_quantify's counters) and one more for the unitig starts; cdbg_reset, a new cdbg_glue and a new cdbg_load_unitigs forget planes and
+ * classes with the index.  The counters of cdbg_quantify and the colours do not touch each other.
+ *   COLOUR SET  colour c is in the colour set of position g if some cdbg_color(c, ...) since the last cdbg_color_open held a valid window
+ *               (inside one sequence, only ACGTacgt) for which cdbg_query reports g; either strand.  In a set that repeats k-mers only the
+ *               smallest occurrence is ever reported: later occurrences keep the empty set.  Marking is idempotent and accumulates.
+ *   RUN         a maximal interval [offset, offset + len) of positions of ONE unitig with equal colour sets.  The runs of a unitig partition
+ *               its LN - k + 1 positions; positions no sample holds form runs too (the empty set).  Runs are ordered by (unitig, offset).
+ *   CLASS       a distinct colour set among the runs, numbered 0, 1, ... in the order of their first run; the empty set is a class like any
+ *               other and has a number only if a run has it.
+ * All results are the same bytes on every run.
+ * cdbg_color_open (builds the index when it is not there): n_colors in 1 .. CDBG_MAX_COLORS (CDBG_E_PARAM otherwise); allocates and zeroes
+ *   the planes (CDBG_E_NOMEM with the sizes in the message when they do not fit), forgets earlier colours and any class result.
+ * cdbg_color: CDBG_E_STATE before an open, color >= n_colors is CDBG_E_PARAM; input as cdbg_quantify takes it.  out (not NULL) = {windows
+ *   looked at, windows found, of those answered from the neighbouring hit without a probe} of this call.  Device memory per call is bounded
+ *   as for cdbg_quantify, with nothing stored per base.  Invalidates the class result.
+ * cdbg_color_classes (CDBG_E_STATE before an open): out (not NULL) = {runs R, classes C, positions with at least one colour, unitigs that
+ *   are one run}; an empty set gives zeros; more than 2^32 - 1 runs is CDBG_E_NOMEM.  A fixed number of launches, whatever the data.
+ * cdbg_fetch_color_runs: the result of the LATEST cdbg_color_classes (CDBG_E_STATE without one): run_off[n_unitigs + 1] -- run_off[u] ..
+ *   run_off[u + 1] are the runs of unitig u -- and per run its offset, length and class (R values each).  Any array may be NULL.
+ * cdbg_fetch_color_classes: classes [first, first + n), a range outside [0, C] is CDBG_E_PARAM: n_colors = colours in the set, runs = runs
+ *   that have it, kmers = positions those runs cover (n values each), bits = n x ceil(N / 32) words, colour c of a class in bit c & 31 of
+ *   its word c >> 5, padding bits zero.  Any array may be NULL. */
+#define CDBG_MAX_COLORS 4096
+int cdbg_color_open(cdbg_ctx* ctx, uint32_t n_colors);
+int cdbg_color(cdbg_ctx* ctx, uint32_t color, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t out[3]);
+int cdbg_color_classes(cdbg_ctx* ctx, uint64_t out[4]);
+int cdbg_fetch_color_runs(cdbg_ctx* ctx, uint64_t* run_off, uint32_t* offset, uint32_t* len, uint32_t* cls);
+int cdbg_fetch_color_classes(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint32_t* n_colors, uint64_t* runs, uint64_t* kmers, uint32_t* bits);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
@@ -381,13 +414,15 @@ int cdbg_fetch_components(cdbg_ctx* ctx, uint32_t* comp, uint64_t first, uint64_
  *   CDBG_POISON_ALLOC=<byte>      every device block newly obtained without a request for zeroing (fresh, or from the process's pool) is
  *                                 filled with that byte (0xFF, 0xA5, ...): no kernel may depend on what a buffer held before.  Read for every
  *                                 new block, never on the path that keeps an existing allocation
- *   CDBG_QUERY_BATCH=<n>          cdbg_query, cdbg_quantify, cdbg_thread: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
+ *   CDBG_QUERY_BATCH=<n>          cdbg_query, cdbg_quantify, cdbg_thread, cdbg_color: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
  *   CDBG_INDEX_LOG2_SLOTS=<n>     cdbg_index: a table of 2^n slots, floored at the smallest power of two > distinct k-mers (and never larger
  *                                 than the default): long probe runs that wrap around the table's end
  *   CDBG_QUANT_CLAMP_WINDOWS=<n>  cdbg_quantify: clamp the counters before more than n windows (default and at most 2^31) were added since the last clamp
- *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify, cdbg_thread: every window probes the index (no window answered by extension)
+ *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify, cdbg_thread, cdbg_color: every window probes the index (no window answered by extension)
  *   CDBG_QUANT_CEILING=<n>        cdbg_quantify / cdbg_fetch_quant: counts are exact below n (default and at most 2^31 - 4096) and reported as 2147483647
- *                                 from there on.  THE ONE HOOK THAT CHANGES REPORTED VALUES: it brings the saturation rule within reach of a test */
+ *                                 from there on.  THE ONE HOOK THAT CHANGES REPORTED VALUES: it brings the saturation rule within reach of a test
+ *   CDBG_COLOR_LOG2_SLOTS=<n>     cdbg_color_classes: a class table of 2^n slots, floored at the smallest power of two > runs (and never larger
+ *                                 than the default, the smallest power of two >= 2 x runs): long probe chains that wrap around the table's end */
 
 #ifdef __cplusplus
 }
