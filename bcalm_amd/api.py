@@ -43,7 +43,7 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-ABI_VERSION = 11                                       # include/cdbg.h CDBG_ABI_VERSION this binding was written for
+ABI_VERSION = 12                                       # include/cdbg.h CDBG_ABI_VERSION this binding was written for
 EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy", "cdbg_release_cached", "cdbg_last_error", "cdbg_push_reads", "cdbg_push_text",
            "cdbg_generate_reads", "cdbg_expect_input", "cdbg_stage_acquire", "cdbg_stage_commit", "cdbg_read_text", "cdbg_count", "cdbg_compact", "cdbg_glue", "cdbg_run", "cdbg_reset",
            "cdbg_num_solid", "cdbg_fetch_solid", "cdbg_num_unitigs", "cdbg_fetch_unitigs", "cdbg_stats", "cdbg_digest", "cdbg_verify",
@@ -51,6 +51,7 @@ EXPORTS = ["cdbg_abi_version", "cdbg_stats_sizeof", "cdbg_create", "cdbg_destroy
            "cdbg_fetch_unitigs_packed", "cdbg_fetch_unitig_abundances", "cdbg_link", "cdbg_num_links", "cdbg_fetch_links", "cdbg_unitig_id_base", "cdbg_load_unitigs", "cdbg_index", "cdbg_index_info", "cdbg_query",
            "cdbg_quantify", "cdbg_fetch_quant", "cdbg_quant_reset", "cdbg_thread", "cdbg_fetch_runs", "cdbg_components", "cdbg_fetch_components",
            "cdbg_color_open", "cdbg_color", "cdbg_color_classes", "cdbg_fetch_color_runs", "cdbg_fetch_color_classes",
+           "cdbg_color_query", "cdbg_fetch_color_query", "cdbg_fetch_color_query_counts",
            "cdbg_set_transport", "cdbg_comm_unique_id", "cdbg_comm_init_rccl", "cdbg_comm_bytes"]
 
 
@@ -130,6 +131,9 @@ def load(path: str | None = None) -> C.CDLL:
     lib.cdbg_color_classes.argtypes = [vp, C.POINTER(u64)]
     lib.cdbg_fetch_color_runs.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     lib.cdbg_fetch_color_classes.argtypes = [vp, u64, u64, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+    lib.cdbg_color_query.argtypes = [vp, C.c_char_p, C.POINTER(u64), u64, u32, u32, i32, C.POINTER(u64)]
+    lib.cdbg_fetch_color_query.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
+    lib.cdbg_fetch_color_query_counts.argtypes = [vp, u64, u64, C.POINTER(u32)]
     lib.cdbg_set_transport.argtypes = [vp, vp]
     lib.cdbg_comm_unique_id.argtypes = [vp]
     lib.cdbg_comm_init_rccl.argtypes = [vp, C.c_char_p]
@@ -152,6 +156,7 @@ class Graph:
                    1 if emit_replicated else 0, 1 if reads_replicated else 0)
         self._h = C.c_void_p()
         self._color = None                                   # (colours opened, totals of cdbg_color_classes or None): see _color_forget()
+        self._color_query = None
         self._ck(self.lib.cdbg_create(C.byref(p), C.byref(self._h)))
 
     def _ck(self, rc):
@@ -371,6 +376,7 @@ class Graph:
     def _color_forget(self):
         """what this object remembers of the library's colours; with every call after which the library has none (reset, run, glue, load)"""
         self._color = None
+        self._color_query = None                             # (sequences of the latest color_query_raw, or None)
 
     def color_open(self, n):
         """n bit planes, one per sample, all empty; earlier colours and classes are forgotten"""
@@ -391,6 +397,7 @@ class Graph:
         out = (C.c_uint64 * 3)()
         if self._color:
             self._color = (self._color[0], None)             # (the library forgets its classes with every further mark)
+        self._color_query = None                             # (... and the query result folded from them)
         self._ck(self.lib.cdbg_color(self._h, color, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), out))
         return {"windows": out[0], "found": out[1], "extended": out[2]}
 
@@ -435,6 +442,62 @@ class Graph:
         """-> per class, in the order of its first run, {"colors": [colour indices], "runs": runs that have it, "kmers": positions they cover}"""
         n, ncol, runs, kmers, bits, nw = self.color_classes_raw()
         return [{"colors": [32 * j + b for j in range(nw) for b in range(32) if (bits[i * nw + j] >> b) & 1], "runs": runs[i], "kmers": kmers[i]} for i in range(n)]
+
+    # ---- pseudoalignment of sequences to the coloured unitigs (cdbg_color_query / cdbg_fetch_color_query / cdbg_fetch_color_query_counts) ----
+    def color_query_raw(self, seqs, share=(0, 1), of_found=False, first_offset=0):
+        """which colours the sequences belong to -> (totals, found, n_colors, bits, words per row, seg_off, seg_start, seg_place, seg_len,
+        seg_class): {windows, found, segments, reported, extended} of the call and ctypes arrays -- per sequence the windows found, the
+        colours reported and their bit row (colour c in bit c & 31 of bits[i * words + (c >> 5)]); seg_off[n + 1] and per segment (a thread
+        run cut where the colour set changes) its first position in the concatenated sequences, the hit word of that position, its length
+        in windows and its class.  share = (num, den): colour c is reported when count[c] >= 1 and count[c] * den >= num * base, base = the
+        windows found with of_found, all len - k + 1 windows otherwise; (0, 1) is the union, (1, 1) with of_found the intersection over
+        the k-mers found.  Replaces the result of thread_raw().  No Python object per k-mer or per segment"""
+        n_colors, _ = self._color_totals()                   # (cdbg_color_classes, once per marked state)
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        off = (C.c_uint64 * (len(bs) + 1))()
+        acc = first_offset
+        for i, b in enumerate(bs):
+            off[i] = acc
+            acc += len(b)
+        off[len(bs)] = acc
+        out = (C.c_uint64 * 5)()
+        self._color_query = None
+        self._ck(self.lib.cdbg_color_query(self._h, b"\n" * first_offset + b"".join(bytes(b) for b in bs), off, len(bs), share[0], share[1], 1 if of_found else 0, out))
+        self._color_query = len(bs)
+        n, S, nw = len(bs), out[2], (n_colors + 31) // 32
+        found, ncol, bits = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n * nw, 1))()
+        seg_off = (C.c_uint64 * (n + 1))()
+        start, place = (C.c_uint64 * max(S, 1))(), (C.c_uint64 * max(S, 1))()
+        ln, cls = (C.c_uint32 * max(S, 1))(), (C.c_uint32 * max(S, 1))()
+        self._ck(self.lib.cdbg_fetch_color_query(self._h, found, ncol, bits, seg_off, start, place, ln, cls))
+        return ({"windows": out[0], "found": out[1], "segments": S, "reported": out[3], "extended": out[4]}, found, ncol, bits, nw, seg_off, start, place, ln, cls)
+
+    def color_query(self, seqs, share=(0, 1), of_found=False):
+        """-> per sequence {"windows": all len - k + 1 of them, "found", "colors": [colour indices reported], "segments": [(q, unitig, offset,
+        strand, n, class)]}: n consecutive k-mers from the sequence's window q on lie on `unitig` from `offset` on (upwards on "+", downwards
+        on "-") inside one colour run of class `class`"""
+        bs = [x if isinstance(x, (bytes, bytearray)) else x.encode() for x in seqs]
+        _, found, ncol, bits, nw, seg_off, start, place, ln, cls = self.color_query_raw(bs, share, of_found)
+        out, at = [], 0
+        for i, b in enumerate(bs):
+            out.append({"windows": max(0, len(b) - self.k + 1), "found": found[i],
+                        "colors": [32 * j + t for j in range(nw) for t in range(32) if (bits[i * nw + j] >> t) & 1],
+                        "segments": [(start[s] - at, place[s] >> 33, (place[s] >> 1) & 0xFFFFFFFF, "-" if place[s] & 1 else "+", ln[s], cls[s])
+                                     for s in range(seg_off[i], seg_off[i + 1])]})
+            at += len(b)
+        return out
+
+    def color_query_counts(self, first=0, count=None):
+        """-> (n, counts, colours): count[c] of the sequences [first, first + count) (default: all from first on) of the latest color_query as
+        the ctypes array counts[n * colours] -- the windows of sequence first + i whose class holds colour c at counts[i * colours + c]"""
+        if self._color_query is None or not self._color:
+            self._ck(self.lib.cdbg_fetch_color_query_counts(self._h, 0, 0, None))    # (the call's own refusal, under its own name)
+            raise CdbgError(-4, "no colour query was run through this Graph: color_query() first")
+        n = self._color_query - first if count is None else count
+        N = self._color[0]
+        counts = (C.c_uint32 * max(n * N, 1))()
+        self._ck(self.lib.cdbg_fetch_color_query_counts(self._h, first, n, counts))
+        return n, counts, N
 
     def _num_unitigs(self):
         n, tb = C.c_uint64(), C.c_uint64()

@@ -42,6 +42,7 @@
 #include "k_thread.h"
 #include "k_components.h"
 #include "k_color.h"
+#include "k_color_query.h"
 
 using namespace cdbg;
 
@@ -57,6 +58,7 @@ using namespace cdbg;
 #include "host_thread.h"
 #include "host_components.h"
 #include "host_color.h"
+#include "host_color_query.h"
 
 
 // =======================================================================================
@@ -334,6 +336,24 @@ int cdbg_fetch_color_classes(cdbg_ctx* c, uint64_t first, uint64_t n, uint32_t* 
     if (!c) return fail(CDBG_E_PARAM, "null context");
     (void)hipSetDevice(c->prm.device_id);
     return fetch_color_classes_impl(c, first, n, n_colors, runs, kmers, bits);
+}
+// ---- pseudoalignment of sequences to the coloured unitigs (k_color_query.h, host_color_query.h) ----
+int cdbg_color_query(cdbg_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t num, uint32_t den, int of_found, uint64_t out[5]) {
+    if (!c || !out || (n_seqs && (!offsets || !bases))) return fail(CDBG_E_PARAM, "null argument");
+    (void)hipSetDevice(c->prm.device_id);
+    try { DISPATCH_WA(color_query_impl, c, bases, offsets, n_seqs, num, den, of_found, out) }
+    catch (...) { thread_forget(c); color_query_forget(c); return fail(CDBG_E_NOMEM, "cdbg_color_query: out of host memory"); }
+}
+int cdbg_fetch_color_query(cdbg_ctx* c, uint32_t* found, uint32_t* n_colors, uint32_t* bits, uint64_t* seg_off, uint64_t* seg_start, uint64_t* seg_place,
+                           uint32_t* seg_len, uint32_t* seg_class) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_color_query_impl(c, found, n_colors, bits, seg_off, seg_start, seg_place, seg_len, seg_class);
+}
+int cdbg_fetch_color_query_counts(cdbg_ctx* c, uint64_t first, uint64_t n, uint32_t* counts) {
+    if (!c) return fail(CDBG_E_PARAM, "null context");
+    (void)hipSetDevice(c->prm.device_id);
+    return fetch_color_query_counts_impl(c, first, n, counts);
 }
 int cdbg_num_links(cdbg_ctx* c, uint64_t* n) {
     if (!c || !n) return fail(CDBG_E_PARAM, "null argument");

@@ -337,6 +337,10 @@ struct cdbg_ctx {
     // [3] unitigs that are one run
     DBuf<uint32_t> color_planes, color_ustart; uint32_t color_n = 0; uint64_t color_words = 0; bool color_opened = false; DBuf<uint64_t> color_out;
     DBuf<uint64_t> cl_run_off, cl_runs, cl_kmers; DBuf<uint32_t> cl_offset, cl_len, cl_cls, cl_ncol, cl_bits; bool cl_ready = false; uint64_t color_info[4] = { 0, 0, 0, 0 };
+    // colour query (host_color_query.h): the result of the latest cdbg_color_query on the device -- found / colours / bit row per sequence, seg_off[n + 1]
+    // and start / place / len / class per segment (24 bytes) -- until the classes it was folded from are forgotten; cq_n sequences, cq_segs segments
+    DBuf<uint64_t> cq_seg_off, cq_seg_start, cq_seg_place; DBuf<uint32_t> cq_seg_len, cq_seg_cls, cq_found, cq_ncol, cq_bits;
+    bool cq_ready = false; uint64_t cq_n = 0, cq_segs = 0;
     DBuf<uint4> rank_a, rank_b; DBuf<uint32_t> rank_flag;
     DBuf<uint4> walk_rec; DBuf<uint32_t> walk_heads, walk_hlen; DBuf<uint64_t> walk_hoff; bool walk_off = false;   // chains walked from their heads (k_walk.h); walk_off: a run of this context had a chain the walk does not take
     // multi-GPU: transport (RCCL or caller-supplied) and the record exchange buffers

@@ -18,8 +18,16 @@ void components_forget(cdbg_ctx* c) {
     for (uint64_t& v : c->comp_info) v = 0;
 }
 
+// what cdbg_color_query keeps for its two fetches (host_color_query.h): it was folded from the classes and goes with them
+void color_query_forget(cdbg_ctx* c) {
+    c->cq_ready = false; c->cq_n = 0; c->cq_segs = 0;
+    c->cq_seg_off.release(); c->cq_seg_start.release(); c->cq_seg_place.release(); c->cq_seg_len.release(); c->cq_seg_cls.release();
+    c->cq_found.release(); c->cq_ncol.release(); c->cq_bits.release();
+}
+
 // the runs and classes cdbg_color_classes keeps for the two colour fetches, and the planes of cdbg_color_open (host_color.h)
 void color_classes_forget(cdbg_ctx* c) {
+    color_query_forget(c);
     c->cl_ready = false;
     c->cl_run_off.release(); c->cl_runs.release(); c->cl_kmers.release(); c->cl_offset.release(); c->cl_len.release(); c->cl_cls.release();
     c->cl_ncol.release(); c->cl_bits.release();

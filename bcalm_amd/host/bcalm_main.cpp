@@ -23,6 +23,8 @@
 //     reads <prefix>.unitigs.fa and the sample files samples.txt names, one per non-empty line (line i is colour i; FASTA / FASTQ, plain or
 //     gzip), marks every sample's k-mers at the unitig positions that spell them (cdbg_load_unitigs + cdbg_color_open + cdbg_color +
 //     cdbg_color_classes) and writes <prefix>.colors.tsv (unitig, offset, len, class per run) and <prefix>.color_classes.tsv.
+//     With -color-query <file> [-color-share num/den] [-color-share-of-found] it then asks which samples every sequence of <file> belongs
+//     to (cdbg_color_query) and writes <prefix>.color_query.tsv: name, k-mers, k-mers found, colours reported, their indices.
 //   ./bcalm -in <prefix|file.unitigs.fa> -kmer-size 31 -components [-out prefix]
 //     reads <prefix>.unitigs.fa, labels the connected components of its records' graph (cdbg_load_unitigs + cdbg_components +
 //     cdbg_fetch_components; links recomputed from the sequences) and writes <prefix>.components.tsv and <prefix>.unitig_components.tsv.
@@ -70,6 +72,9 @@ struct Options {
     std::string quantify;                            // -quantify <file>: count the k-mers of its sequences per unitig of an existing <prefix>.unitigs.fa
     std::string thread;                              // -thread <file>: the runs of its sequences' k-mers along the unitigs of an existing <prefix>.unitigs.fa
     std::string colors;                              // -colors <list>: one sample file per line; colour the unitigs of an existing <prefix>.unitigs.fa by sample
+    std::string color_query;                         // -color-query <file> (with -colors): which samples every sequence of the file belongs to
+    uint32_t share_num = 0, share_den = 1;           // -color-share num/den: a colour is reported when it holds at least that share of the sequence's k-mers (0/1: any)
+    bool share_of_found = false;                     // -color-share-of-found: ... of the k-mers found in the graph, not of all of them
     bool components = false;                         // -components: the connected components of the records of an existing <prefix>.unitigs.fa
     std::string query;                               // -query <file>: look the k-mers of its sequences up in an existing <prefix>.unitigs.fa
 };
@@ -100,6 +105,17 @@ Options parse(int argc, char** argv) {
         else if (a == "-thread") o.thread = need("-thread");
         else if (a == "-components") o.components = true;
         else if (a == "-colors") o.colors = need("-colors");
+        else if (a == "-color-query") o.color_query = need("-color-query");
+        else if (a == "-color-share-of-found") o.share_of_found = true;
+        else if (a == "-color-share") {                               // num/den, two decimal numbers, 0 <= num <= den <= 2^32 - 1, den >= 1
+            const std::string v = need("-color-share");
+            const size_t sl = v.find('/');
+            const std::string a0 = v.substr(0, sl), a1 = sl == std::string::npos ? "" : v.substr(sl + 1);
+            auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 10 && t.find_first_not_of("0123456789") == std::string::npos; };
+            const unsigned long long nu = digits(a0) ? strtoull(a0.c_str(), nullptr, 10) : ~0ull, de = digits(a1) ? strtoull(a1.c_str(), nullptr, 10) : ~0ull;
+            if (nu > 0xFFFFFFFFull || de > 0xFFFFFFFFull || de < 1 || nu > de) usage_error("malformed -color-share '" + v + "': num/den with 0 <= num <= den, den >= 1");
+            o.share_num = (uint32_t)nu; o.share_den = (uint32_t)de;
+        }
         else if (a == "-skip-bcalm") o.skip_bcalm = true;
         else if (a == "-skip-bglue") o.skip_bglue = true;
         else if (a == "-no-stream-scan") o.no_stream = true;           // dev: do not announce the input volume (the read scan starts when the text is complete)
@@ -959,7 +975,8 @@ int colors_mode(const Options& o, const std::string& prefix, int threads) {
     if (samples.empty()) usage_error("-colors: no samples in " + o.colors);
     if (samples.size() > CDBG_MAX_COLORS) usage_error("-colors: " + std::to_string(samples.size()) + " samples in " + o.colors + ", at most " + std::to_string(CDBG_MAX_COLORS) + " (CDBG_MAX_COLORS)");
     for (const std::string& sf : samples) { FILE* f = fopen(sf.c_str(), "rb"); if (!f) usage_error("cannot open sample file " + sf); fclose(f); }
-    const std::string fa = prefix + ".unitigs.fa", rtsv = prefix + ".colors.tsv", ctsv = prefix + ".color_classes.tsv";
+    if (!o.color_query.empty()) { FILE* f = fopen(o.color_query.c_str(), "rb"); if (!f) usage_error("cannot open query file " + o.color_query); fclose(f); }
+    const std::string fa = prefix + ".unitigs.fa", rtsv = prefix + ".colors.tsv", ctsv = prefix + ".color_classes.tsv", qtsv = prefix + ".color_query.tsv";
     UnitigFile F; read_unitig_file(o, fa, threads, "-colors", F);
     cdbg_ctx* ctx = load_unitig_file(o, fa, F);
     struct Guard { cdbg_ctx* c; ~Guard() { cdbg_destroy(c); } } guard{ ctx };
@@ -1006,7 +1023,7 @@ int colors_mode(const Options& o, const std::string& prefix, int threads) {
         void open(const std::string& n) { f = fopen(n.c_str(), "w"); if (!f) usage_error("cannot write " + n); name = n; }
         bool close() { FILE* g = f; f = nullptr; return !g || fclose(g) == 0; }
         bool commit(const std::string& to) { if (rename(name.c_str(), to.c_str()) != 0) return false; name.clear(); return true; }
-    } tr, tc;
+    } tr, tc, tq;
     tr.open(rtsv + ".tmp" + std::to_string((long)getpid())); tc.open(ctsv + ".tmp" + std::to_string((long)getpid()));
     auto put_u = [](std::string& d, unsigned long long v) { char t[24]; int n = 0; do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) d.push_back(t[--n]); };
     bool wfail = false; std::string out;
@@ -1036,6 +1053,52 @@ int colors_mode(const Options& o, const std::string& prefix, int threads) {
     printf("colors: %u samples, %llu k-mers, %llu found, %llu runs, %llu classes (load %.2f s, index %.2f s, mark %.2f s, classes %.2f s)\n", N, (unsigned long long)tot[0],
            (unsigned long long)tot[1], (unsigned long long)R, (unsigned long long)NC, secs(t0, t1), secs(t1, t2), secs(t2, t3), secs(t3, t4));
     printf("colours written to %s and %s\n", rtsv.c_str(), ctsv.c_str());
+    if (o.color_query.empty()) return EXIT_SUCCESS;
+    // -color-query: name, windows, found, colours reported, their indices ('*' for none) per sequence, in batches of 64 MB of bases
+    tq.open(qtsv + ".tmp" + std::to_string((long)getpid()));
+    const uint64_t K = (uint64_t)o.k;
+    std::string bases; std::vector<std::string> names; std::vector<uint64_t> off{ 0 }; std::vector<uint32_t> q_found, q_ncol, q_bits;
+    uint64_t n_seqs = 0, n_kmers = 0, n_found = 0, n_segs = 0, n_rep = 0; double query_s = 0;
+    auto flush = [&]() {
+        if (names.empty()) return;
+        uint64_t qt[5];
+        const auto q0 = clk::now();
+        check(cdbg_color_query(ctx, bases.data(), off.data(), names.size(), o.share_num, o.share_den, o.share_of_found ? 1 : 0, qt));
+        q_found.resize(names.size()); q_ncol.resize(names.size()); q_bits.resize(names.size() * NW);
+        check(cdbg_fetch_color_query(ctx, q_found.data(), q_ncol.data(), q_bits.data(), nullptr, nullptr, nullptr, nullptr, nullptr));
+        query_s += secs(q0, clk::now());
+        out.clear();
+        for (size_t i = 0; i < names.size(); ++i) {
+            const uint64_t n = off[i + 1] - off[i], nk = n >= K ? n - K + 1 : 0;
+            out.append(names[i]); out.push_back('\t'); put_u(out, nk); out.push_back('\t'); put_u(out, q_found[i]); out.push_back('\t'); put_u(out, q_ncol[i]); out.push_back('\t');
+            bool first = true;
+            for (uint32_t col = 0; col < N; ++col)
+                if ((q_bits[i * NW + (col >> 5)] >> (col & 31)) & 1u) { if (!first) out.push_back(','); put_u(out, col); first = false; }
+            if (first) out.push_back('*');
+            out.push_back('\n');
+            n_kmers += nk;
+        }
+        flush_out(tq.f, true);
+        n_seqs += names.size(); n_found += qt[1]; n_segs += qt[2]; n_rep += qt[3];
+        names.clear(); bases.clear(); off.assign(1, 0);
+    };
+    parse_queries(o.color_query, bases, [&](const std::string& name) {
+        if (bases.size() > BATCH && !names.empty()) {              // this record would pass 64 MB of bases: what came before it goes first
+            const std::string last = bases.substr(off.back());
+            bases.resize(off.back());
+            flush();
+            bases = last;
+        }
+        names.push_back(name); off.push_back(bases.size());
+    });
+    flush();
+    if (!tq.close()) wfail = true;
+    if (wfail) usage_error("write error on " + tq.name);
+    if (!tq.commit(qtsv)) usage_error("cannot rename " + tq.name + " to " + qtsv);
+    printf("color-query: %llu sequences, %llu k-mers, %llu found, %llu segments, %llu sequences with a colour, share %u/%u of %s (query %.2f s)\n", (unsigned long long)n_seqs,
+           (unsigned long long)n_kmers, (unsigned long long)n_found, (unsigned long long)n_segs, (unsigned long long)n_rep, o.share_num, o.share_den,
+           o.share_of_found ? "the k-mers found" : "all k-mers", query_s);
+    printf("colour query written to %s\n", qtsv.c_str());
     return EXIT_SUCCESS;
 }
 
@@ -1128,6 +1191,7 @@ int main(int argc, char** argv) {
         std::string prefix = o.out.empty() ? base_name(o.in) : o.out;
         if ((o.skip_bcalm || o.skip_bglue) && !o.redo_links) usage_error("-skip-bcalm and -skip-bglue are only supported together with -redo-links (no glue files are kept between runs)");
         if (!o.colors.empty() && (o.components || !o.thread.empty() || !o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-colors, -components, -thread, -query, -quantify and -redo-links are separate modes: give one of them");
+        if (!o.color_query.empty() && o.colors.empty()) usage_error("-color-query needs -colors <list>: the samples whose colours the sequences are asked for");
         if (!o.colors.empty() && o.n_gpus != 1) usage_error("-colors runs on one GPU: -nb-gpus must be 1");
         if (o.components && (!o.thread.empty() || !o.query.empty() || !o.quantify.empty() || o.redo_links)) usage_error("-components, -thread, -query, -quantify and -redo-links are separate modes: give one of them");
         if (o.components && o.n_gpus != 1) usage_error("-components runs on one GPU: -nb-gpus must be 1");

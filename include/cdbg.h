@@ -85,7 +85,7 @@ typedef struct cdbg_stats_t {
 /* ABI version: bumped whenever a struct of this header changes.  From version 5 on cdbg_stats_t only ever GROWS AT ITS END;
  * a binding checks cdbg_abi_version() against the header it was written for and sizeof(cdbg_stats_t) against
  * cdbg_stats_sizeof() when it loads the library (bcalm_amd/api.py does), instead of reading fields at stale offsets. */
-#define CDBG_ABI_VERSION 11
+#define CDBG_ABI_VERSION 12
 int cdbg_abi_version(void);
 uint64_t cdbg_stats_sizeof(void);
 
@@ -400,6 +400,38 @@ int cdbg_color_classes(cdbg_ctx* ctx, uint64_t out[4]);
 int cdbg_fetch_color_runs(cdbg_ctx* ctx, uint64_t* run_off, uint32_t* offset, uint32_t* len, uint32_t* cls);
 int cdbg_fetch_color_classes(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint32_t* n_colors, uint64_t* runs, uint64_t* kmers, uint32_t* bits);
 
+/* Colour query (pseudoalignment): which of the N samples a read, a contig or a gene belongs to -- the walk of every sequence through the
+ * graph joined with the colour runs, and the fold of the joined pieces per sequence, on the device (bcalm_amd/csrc/k_color_query.h).
+ * Input is as cdbg_thread takes it; positions are numbered in the concatenated input from offsets[0]; hit words are as cdbg_query reports.
+ *   SEGMENT     position g continues g - 1 when cdbg_thread's definition says so AND both hits lie in the same colour run of the latest
+ *               cdbg_color_classes.  A segment is a maximal chain of continuing positions: start = its first position, place = the hit word
+ *               of that position, len = its windows, cls = the class of its colour run.  Segments are thread runs cut where the colour set
+ *               changes; on strand 1 a segment walks its unitig downwards, so the colour runs of a unitig appear in reverse order.  Segments
+ *               lie in position order and none spans two sequences.
+ *   PER SEQUENCE i   total_i = max(0, length_i - k + 1): every window counts, a window over a byte outside ACGTacgt is a k-mer the graph
+ *               does not have.  found_i = the sum of its segments' len.  count_i[c] = the sum of len over its segments whose class holds c.
+ *   REPORTED    colour c is reported for sequence i under (num, den, of_found) when count_i[c] >= 1 and count_i[c] * den >= num * base_i in
+ *               64-bit arithmetic, base_i = found_i when of_found != 0 and total_i otherwise.  num = 0: the union of the colours seen;
+ *               num = den with of_found: the intersection over the k-mers found.  A sequence with base_i = 0 reports nothing.
+ * cdbg_color_query: CDBG_E_STATE before cdbg_color_classes and after anything that forgets the classes (a further cdbg_color,
+ *   cdbg_color_open, cdbg_reset, cdbg_run, cdbg_glue, cdbg_load_unitigs: each forgets the query result too).  num > den or den == 0, and a
+ *   sequence of more than 2^32 - 1 windows, are CDBG_E_PARAM; what does not fit is CDBG_E_NOMEM with the sizes in the message; a failed
+ *   call leaves no result behind.  out (not NULL) = {valid windows, windows found, segments S, sequences with at least one colour reported,
+ *   windows answered by extension}.  THE CALL RUNS cdbg_thread ON ITS INPUT and, like another cdbg_thread, replaces that call's result:
+ *   cdbg_fetch_runs then reports the runs of these sequences.  A later cdbg_thread does not touch the colour query's own buffers.  Device
+ *   memory: 20 bytes per thread run and 16 per sequence while the call runs; 24 bytes per segment and 12 + 4 ceil(N / 32) per sequence stay.
+ *   A fixed number of launches, whatever the data; the same bytes on every run.
+ * cdbg_fetch_color_query (CDBG_E_STATE without a query): per sequence found, n_colors = colours reported and bits[n_seqs][ceil(N / 32)]
+ *   (colour c in bit c & 31 of word c >> 5, padding bits zero); seg_off[n_seqs + 1] -- seg_off[i] .. seg_off[i + 1] are the segments of
+ *   sequence i -- and per segment start, place, len, class (S values each).  Any pointer may be NULL.
+ * cdbg_fetch_color_query_counts: count_i[c] of the sequences [first, first + n) as counts[n][N]; a range outside [0, n_seqs] is
+ *   CDBG_E_PARAM.  The matrix is never kept (n_seqs x N x 4 bytes is 16 GB at a million reads and 4096 colours): the call folds the range
+ *   again into a temporary of the range's size. */
+int cdbg_color_query(cdbg_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t num, uint32_t den, int of_found, uint64_t out[5]);
+int cdbg_fetch_color_query(cdbg_ctx* ctx, uint32_t* found, uint32_t* n_colors, uint32_t* bits, uint64_t* seg_off, uint64_t* seg_start, uint64_t* seg_place,
+                           uint32_t* seg_len, uint32_t* seg_class);
+int cdbg_fetch_color_query_counts(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint32_t* counts);
+
 /* Environment variables read by the library -- test hooks that force paths an ordinary input does not reach (tests/), not
  * tuning knobs; results are identical with and without them:
  *   CDBG_SCAN_MODE=capped|exact|var  record layout (default: by input size and skew; var = one pass into per-partition regions sized
@@ -414,11 +446,11 @@ int cdbg_fetch_color_classes(cdbg_ctx* ctx, uint64_t first, uint64_t n, uint32_t
  *   CDBG_POISON_ALLOC=<byte>      every device block newly obtained without a request for zeroing (fresh, or from the process's pool) is
  *                                 filled with that byte (0xFF, 0xA5, ...): no kernel may depend on what a buffer held before.  Read for every
  *                                 new block, never on the path that keeps an existing allocation
- *   CDBG_QUERY_BATCH=<n>          cdbg_query, cdbg_quantify, cdbg_thread, cdbg_color: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
+ *   CDBG_QUERY_BATCH=<n>          cdbg_query, cdbg_quantify, cdbg_thread, cdbg_color, cdbg_color_query: bases per device batch (floor max(4 k, 256)): a sequence then spans many batches
  *   CDBG_INDEX_LOG2_SLOTS=<n>     cdbg_index: a table of 2^n slots, floored at the smallest power of two > distinct k-mers (and never larger
  *                                 than the default): long probe runs that wrap around the table's end
  *   CDBG_QUANT_CLAMP_WINDOWS=<n>  cdbg_quantify: clamp the counters before more than n windows (default and at most 2^31) were added since the last clamp
- *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify, cdbg_thread, cdbg_color: every window probes the index (no window answered by extension)
+ *   CDBG_QUANT_NO_EXTEND=1        cdbg_quantify, cdbg_thread, cdbg_color, cdbg_color_query: every window probes the index (no window answered by extension)
  *   CDBG_QUANT_CEILING=<n>        cdbg_quantify / cdbg_fetch_quant: counts are exact below n (default and at most 2^31 - 4096) and reported as 2147483647
  *                                 from there on.  THE ONE HOOK THAT CHANGES REPORTED VALUES: it brings the saturation rule within reach of a test
  *   CDBG_COLOR_LOG2_SLOTS=<n>     cdbg_color_classes: a class table of 2^n slots, floored at the smallest power of two > runs (and never larger
