@@ -53,6 +53,7 @@ using namespace cdbg;
 #include "host_glue_sharded.h"
 #include "host_glue.h"
 #include "host_relink.h"
+#include "host_window.h"
 #include "host_index.h"
 #include "host_quant.h"
 #include "host_thread.h"

@@ -39,59 +39,27 @@ int color_impl(cdbg_ctx* c, uint32_t color, const char* bases, const uint64_t* o
     out[0] = out[1] = out[2] = 0;
     if (!c->color_opened) return fail(CDBG_E_STATE, "cdbg_color before cdbg_color_open");
     if (color >= c->color_n) return fail(CDBG_E_PARAM, "cdbg_color: colour %u of %u", color, c->color_n);
-    for (uint64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return fail(CDBG_E_PARAM, "cdbg_color: offsets not monotone at sequence %llu", (unsigned long long)i);
+    CK(check_offsets("cdbg_color", off, n));
     color_classes_forget(c);
-    const uint64_t base0 = n ? off[0] : 0, total = n ? off[n] - base0 : 0;
+    const uint64_t total = n ? off[n] - off[0] : 0;
     if (!total) return CDBG_OK;
-    const uint64_t k = (uint64_t)c->k, PW = c->color_words;
-    // bases per device batch (text + sequence ends, nothing per base); consecutive batches overlap by k - 1 bases, and the windows that
-    // start in a batch's last k - 1 bases belong to the next one (marking twice would be harmless; the totals would count twice)
-    uint64_t B = 64ull << 20;
-    if (const char* e = c->knobs.get("CDBG_QUERY_BATCH")) B = strtoull(e, nullptr, 10);
-    B = std::min<uint64_t>(std::max<uint64_t>(B, std::max<uint64_t>(4 * k, 256)), 1ull << 31);
-    // extension only in a set that spells every k-mer once: elsewhere the neighbour of a hit need not be the smallest occurrence
-    const int extend = (c->index_info[0] == c->index_info[1] && !c->knobs.get("CDBG_QUANT_NO_EXTEND")) ? 1 : 0;
-    CK(ingest_init(c));                                      // the pinned staging pair and its copy stream
+    const uint64_t PW = c->color_words;
     hipStream_t s = c->stream;
     CK(c->color_out.alloc(4, false));
     HIPCK(hipMemsetAsync(c->color_out.p, 0, 4 * sizeof(uint64_t), s));
-    std::vector<uint32_t> bnd;
     const bool marks = HostMarks::enabled();
     float ms_kernels = 0;
-    for (uint64_t b0 = 0; b0 < total;) {
-        const uint64_t b1 = std::min(total, b0 + B), nb = b1 - b0;
-        const uint64_t n_out = b1 == total ? nb : nb - (k - 1);
-        CK(c->q_text.alloc(nb, false));
-        int pb = 0; bool busy[2] = { false, false };
-        for (uint64_t d = 0; d < nb; d += cdbg_ctx::STAGE_BYTES, pb ^= 1) {
-            const uint64_t m = std::min<uint64_t>(cdbg_ctx::STAGE_BYTES, nb - d);
-            if (busy[pb]) HIPCK(hipEventSynchronize(c->pin_ev[pb]));
-            memcpy(c->pin[pb], bases + base0 + b0 + d, m);
-            HIPCK(hipMemcpyAsync(c->q_text.p + d, c->pin[pb], m, hipMemcpyHostToDevice, c->copy_stream));
-            HIPCK(hipEventRecord(c->pin_ev[pb], c->copy_stream));
-            busy[pb] = true;
-        }
-        // the sequence ends inside the batch, in its own coordinates (a run of empty sequences is one end), closed by the batch's end
-        bnd.clear();
-        for (const uint64_t* it = std::upper_bound(off, off + n + 1, base0 + b0); it < off + n + 1 && *it < base0 + b1; ++it) {
-            const uint32_t v = (uint32_t)(*it - base0 - b0);
-            if (bnd.empty() || bnd.back() != v) bnd.push_back(v);
-        }
-        bnd.push_back((uint32_t)nb);
-        CK(c->q_bnd.alloc(bnd.size(), false));
-        HIPCK(hipMemcpy(c->q_bnd.p, bnd.data(), bnd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCK(hipStreamSynchronize(c->copy_stream));
+    // per base of a batch: text + sequence ends, nothing else (marking a window in two batches would be harmless; the totals would count twice)
+    CK(window_batches(c, bases, off, n, [&](uint64_t, uint64_t, uint64_t n_out, const WindowParams& wp) -> int {
         ColorMarkParams mp{};
-        mp.text = c->q_text.p; mp.n_text = nb; mp.n_out = n_out; mp.bnd = c->q_bnd.p; mp.n_bnd = (uint32_t)bnd.size(); mp.k = c->k; mp.extend = extend;
-        mp.packed = c->unitig_packed.p; mp.unitig_off = c->unitig_off.p; mp.unitig_len = c->unitig_len.p; mp.kmer_off = c->kmer_off.p;
-        mp.slots = c->index_slots.p; mp.mask = c->index_info[2] - 1; mp.plane = c->color_planes.p + (uint64_t)color * PW; mp.n_words = PW; mp.out = c->color_out.p;
+        (WindowParams&)mp = wp; mp.plane = c->color_planes.p + (uint64_t)color * PW; mp.n_words = PW; mp.out = c->color_out.p;
         Timer t; if (marks) CK(t.start(s));
         CDBG_LAUNCH((k_color_mark<W>), (n_out + QUANT_TILE - 1) / QUANT_TILE, QUANT_THREADS, s, mp);
         if (marks) { float ms = 0; CK(t.stop(&ms)); ms_kernels += ms; }
         HIPCK(hipStreamSynchronize(s));                      // (the next batch overwrites the text)
         HIPCK(hipGetLastError());
-        b0 += n_out;
-    }
+        return CDBG_OK;
+    }));
     uint64_t o[4] = { 0, 0, 0, 0 };
     CK(read_u64(c->color_out.p, o, 4));
     out[0] = o[0]; out[1] = o[1]; out[2] = o[2];

@@ -22,8 +22,8 @@ int color_query_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64
     if (!c->cl_ready) return fail(CDBG_E_STATE, "cdbg_color_query before cdbg_color_classes");
     if (den < 1 || num > den) return fail(CDBG_E_PARAM, "cdbg_color_query: share %u / %u (0 <= num <= den, den >= 1)", num, den);
     const uint64_t k = (uint64_t)c->k;
+    CK(check_offsets("cdbg_color_query", off, n));
     for (uint64_t i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i]) return fail(CDBG_E_PARAM, "cdbg_color_query: offsets not monotone at sequence %llu", (unsigned long long)i);
         const uint64_t len = off[i + 1] - off[i];
         if (len >= k && len - k + 1 > 0xFFFFFFFFull)
             return fail(CDBG_E_PARAM, "cdbg_color_query: sequence %llu has %llu windows, more than the 4294967295 a 32-bit count holds", (unsigned long long)i, (unsigned long long)(len - k + 1));

@@ -108,18 +108,11 @@ template <int W>
 int query_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64_t n, uint64_t* hits) {
     CK(index_refuse(c, "cdbg_query"));
     if (!n) return CDBG_OK;
-    for (uint64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return fail(CDBG_E_PARAM, "cdbg_query: offsets not monotone at sequence %llu", (unsigned long long)i);
-    const uint64_t base0 = off[0], total = off[n] - base0;
+    CK(check_offsets("cdbg_query", off, n));
+    const uint64_t total = off[n] - off[0];
     if (!total) return CDBG_OK;
     CK(index_impl<W>(c, "cdbg_query"));
-    const uint64_t k = (uint64_t)c->k;
-    // bases per device batch (text + sequence ends + 8 bytes of hits per base); consecutive batches overlap by k - 1 bases
-    uint64_t B = 64ull << 20;
-    if (const char* e = c->knobs.get("CDBG_QUERY_BATCH")) B = strtoull(e, nullptr, 10);
-    B = std::min<uint64_t>(std::max<uint64_t>(B, std::max<uint64_t>(4 * k, 256)), 1ull << 31);
-    CK(ingest_init(c));                                      // the pinned staging pair and its copy stream
     hipStream_t s = c->stream;
-    std::vector<uint32_t> bnd;
     const bool marks = HostMarks::enabled();
     float ms_kernels = 0;
 #ifdef CDBG_PROFILE_PHASES
@@ -127,41 +120,19 @@ int query_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64_t n, 
 #else
     CK(c->q_prof.alloc(2, false));
 #endif
-    for (uint64_t b0 = 0; b0 < total;) {
-        const uint64_t b1 = std::min(total, b0 + B), nb = b1 - b0;
-        const uint64_t n_out = b1 == total ? nb : nb - (k - 1);
-        CK(c->q_text.alloc(nb, false)); CK(c->q_hits.alloc(n_out, false));
-        int pb = 0; bool busy[2] = { false, false };
-        for (uint64_t d = 0; d < nb; d += cdbg_ctx::STAGE_BYTES, pb ^= 1) {
-            const uint64_t m = std::min<uint64_t>(cdbg_ctx::STAGE_BYTES, nb - d);
-            if (busy[pb]) HIPCK(hipEventSynchronize(c->pin_ev[pb]));
-            memcpy(c->pin[pb], bases + base0 + b0 + d, m);
-            HIPCK(hipMemcpyAsync(c->q_text.p + d, c->pin[pb], m, hipMemcpyHostToDevice, c->copy_stream));
-            HIPCK(hipEventRecord(c->pin_ev[pb], c->copy_stream));
-            busy[pb] = true;
-        }
-        // the sequence ends inside the batch, in its own coordinates (a run of empty sequences is one end), closed by the batch's end
-        bnd.clear();
-        for (const uint64_t* it = std::upper_bound(off, off + n + 1, base0 + b0); it < off + n + 1 && *it < base0 + b1; ++it) {
-            const uint32_t v = (uint32_t)(*it - base0 - b0);
-            if (bnd.empty() || bnd.back() != v) bnd.push_back(v);
-        }
-        bnd.push_back((uint32_t)nb);
-        CK(c->q_bnd.alloc(bnd.size(), false));
-        HIPCK(hipMemcpy(c->q_bnd.p, bnd.data(), bnd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCK(hipStreamSynchronize(c->copy_stream));
+    // per base of a batch: text + sequence ends + 8 bytes of hits
+    CK(window_batches(c, bases, off, n, [&](uint64_t b0, uint64_t, uint64_t n_out, const WindowParams& wp) -> int {
+        CK(c->q_hits.alloc(n_out, false));
         QueryParams qp{};
-        qp.text = c->q_text.p; qp.n_text = nb; qp.n_out = n_out; qp.bnd = c->q_bnd.p; qp.n_bnd = (uint32_t)bnd.size(); qp.k = c->k;
-        qp.packed = c->unitig_packed.p; qp.unitig_off = c->unitig_off.p; qp.slots = c->index_slots.p; qp.mask = c->index_info[2] - 1;
-        qp.hits = c->q_hits.p; qp.out = c->q_prof.p;
+        (WindowParams&)qp = wp; qp.hits = c->q_hits.p; qp.out = c->q_prof.p;
         Timer t; if (marks) CK(t.start(s));
         CDBG_LAUNCH((k_query<W>), (n_out + QUERY_TILE - 1) / QUERY_TILE, QUERY_THREADS, s, qp);
         if (marks) { float ms = 0; CK(t.stop(&ms)); ms_kernels += ms; }
         HIPCK(hipStreamSynchronize(s));
         HIPCK(hipGetLastError());
         HIPCK(hipMemcpy(hits + b0, c->q_hits.p, n_out * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        b0 += n_out;
-    }
+        return CDBG_OK;
+    }));
     if (marks) {                                             // dev aid (CDBG_HOST_MARKS=1; bench_micro/query_timing.py reads it)
         uint64_t pr[2] = { 0, 0 };
 #ifdef CDBG_PROFILE_PHASES

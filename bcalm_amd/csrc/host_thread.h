@@ -5,65 +5,27 @@
 
 namespace {
 
-// the definition of k_thread.h on the host, for the seams: does hit word b, one position behind hit word a, continue a's run
-bool thread_continues_host(uint64_t a, uint64_t b) {
-    if (a == ~0ull || b == ~0ull || (a >> 33) != (b >> 33) || ((a ^ b) & 1)) return false;
-    const uint64_t oa = (a >> 1) & 0xFFFFFFFFull, ob = (b >> 1) & 0xFFFFFFFFull;
-    return (a & 1) ? ob + 1 == oa : ob == oa + 1;
-}
-
 template <int W>
 int thread_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64_t n, uint64_t* out) {
     CK(index_refuse(c, "cdbg_thread"));
     out[0] = out[1] = out[2] = out[3] = 0;
-    for (uint64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return fail(CDBG_E_PARAM, "cdbg_thread: offsets not monotone at sequence %llu", (unsigned long long)i);
+    CK(check_offsets("cdbg_thread", off, n));
     thread_forget(c);                                        // (a call that fails leaves no result behind)
     CK(index_impl<W>(c, "cdbg_thread"));
     const uint64_t base0 = n ? off[0] : 0, total = n ? off[n] - base0 : 0;
-    const uint64_t k = (uint64_t)c->k;
-    // bases per device batch (text + sequence ends + 8 bytes of hits per base, which stay there); consecutive batches overlap by k - 1 bases
-    uint64_t B = 64ull << 20;
-    if (const char* e = c->knobs.get("CDBG_QUERY_BATCH")) B = strtoull(e, nullptr, 10);
-    B = std::min<uint64_t>(std::max<uint64_t>(B, std::max<uint64_t>(4 * k, 256)), 1ull << 31);
-    // extension only in a set that spells every k-mer once: elsewhere the neighbour of a hit need not be the smallest occurrence
-    const int extend = (c->index_info[0] == c->index_info[1] && !c->knobs.get("CDBG_QUANT_NO_EXTEND")) ? 1 : 0;
     hipStream_t s = c->stream;
-    std::vector<uint32_t> bnd;
     const bool marks = HostMarks::enabled();
     float ms_hits = 0, ms_runs = 0;
     if (total) {
-        CK(ingest_init(c));                                  // the pinned staging pair and its copy stream
         CK(c->th_out.alloc(4, false));
         HIPCK(hipMemsetAsync(c->th_out.p, 0, 4 * sizeof(uint64_t), s));
     }
-    for (uint64_t b0 = 0; b0 < total;) {
-        const uint64_t b1 = std::min(total, b0 + B), nb = b1 - b0;
-        const uint64_t n_out = b1 == total ? nb : nb - (k - 1);
-        CK(c->q_text.alloc(nb, false)); CK(c->q_hits.alloc(n_out, false));
-        int pb = 0; bool busy[2] = { false, false };
-        for (uint64_t d = 0; d < nb; d += cdbg_ctx::STAGE_BYTES, pb ^= 1) {
-            const uint64_t m = std::min<uint64_t>(cdbg_ctx::STAGE_BYTES, nb - d);
-            if (busy[pb]) HIPCK(hipEventSynchronize(c->pin_ev[pb]));
-            memcpy(c->pin[pb], bases + base0 + b0 + d, m);
-            HIPCK(hipMemcpyAsync(c->q_text.p + d, c->pin[pb], m, hipMemcpyHostToDevice, c->copy_stream));
-            HIPCK(hipEventRecord(c->pin_ev[pb], c->copy_stream));
-            busy[pb] = true;
-        }
-        // the sequence ends inside the batch, in its own coordinates (a run of empty sequences is one end), closed by the batch's end
-        bnd.clear();
-        for (const uint64_t* it = std::upper_bound(off, off + n + 1, base0 + b0); it < off + n + 1 && *it < base0 + b1; ++it) {
-            const uint32_t v = (uint32_t)(*it - base0 - b0);
-            if (bnd.empty() || bnd.back() != v) bnd.push_back(v);
-        }
-        bnd.push_back((uint32_t)nb);
-        CK(c->q_bnd.alloc(bnd.size(), false));
-        HIPCK(hipMemcpy(c->q_bnd.p, bnd.data(), bnd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCK(hipStreamSynchronize(c->copy_stream));
+    // per base of a batch: text + sequence ends + 8 bytes of hits, which stay on the device
+    CK(window_batches(c, bases, off, n, [&](uint64_t b0, uint64_t, uint64_t n_out, const WindowParams& wp) -> int {
         // 1. the hit word of every position of the batch, into q_hits
+        CK(c->q_hits.alloc(n_out, false));
         ThreadHitParams hp{};
-        hp.text = c->q_text.p; hp.n_text = nb; hp.n_out = n_out; hp.bnd = c->q_bnd.p; hp.n_bnd = (uint32_t)bnd.size(); hp.k = c->k; hp.extend = extend;
-        hp.packed = c->unitig_packed.p; hp.unitig_off = c->unitig_off.p; hp.unitig_len = c->unitig_len.p;
-        hp.slots = c->index_slots.p; hp.mask = c->index_info[2] - 1; hp.hits = c->q_hits.p; hp.out = c->th_out.p;
+        (WindowParams&)hp = wp; hp.hits = c->q_hits.p; hp.out = c->th_out.p;
         Timer t; if (marks) CK(t.start(s));
         CDBG_LAUNCH((k_thread_hits<W>), (n_out + QUERY_TILE - 1) / QUERY_TILE, QUERY_THREADS, s, hp);
         if (marks) { float ms = 0; CK(t.stop(&ms)); ms_hits += ms; CK(t.start(s)); }
@@ -97,14 +59,14 @@ int thread_impl(cdbg_ctx* c, const char* bases, const uint64_t* off, uint64_t n,
             // the seam: the last run before this batch goes on in the batch's first run when the definition says that it continues
             if (have && c->run_start[have] == c->run_start[have - 1] + c->run_len[have - 1]) {
                 const uint64_t a = c->run_place[have - 1], steps = (uint64_t)(c->run_len[have - 1] - 1u) << 1;
-                if (thread_continues_host((a & 1) ? a - steps : a + steps, c->run_place[have])) {
+                if (thread_continues((a & 1) ? a - steps : a + steps, c->run_place[have])) {
                     c->run_len[have - 1] += c->run_len[have];
                     c->run_start.erase(c->run_start.begin() + have); c->run_place.erase(c->run_place.begin() + have); c->run_len.erase(c->run_len.begin() + have);
                 }
             }
         }
-        b0 += n_out;
-    }
+        return CDBG_OK;
+    }));
     uint64_t o[3] = { 0, 0, 0 };
     if (total) CK(read_u64(c->th_out.p, o, 3));
     // the runs of sequence i: those that start inside it (runs lie in position order; no run spans two sequences)

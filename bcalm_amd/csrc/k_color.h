@@ -5,13 +5,13 @@
 // N BIT PLANES OF P BITS, COLOUR-MAJOR: plane[c][g >> 5] bit g & 31, g = kmer_off[u] + offset as the index and cdbg_quantify number the
 // positions.  Neighbouring positions of a unitig share a word, and "does the colour set change between g - 1 and g" is a word operation:
 // ustart | OR_c (x_c ^ ((x_c << 1) | bit 31 of the word before)).  One more plane, ustart, holds a bit at every kmer_off[u].
-//   k_color_mark<W>   k_quant's tile (2-bit codes with a k - 1 halo in LDS, QUANT_RUN consecutive windows per lane, one probe and then
-//                     extension from ONE arena base) with a different ending: instead of one atomic add per hit a lane keeps (word index,
-//                     mask) in registers, ORs the hit's bit into the mask and writes the mask with one atomic OR when the word index
-//                     changes -- hits walk up on strand 0 and down on strand 1 -- and at the end of its run.  (A miss does not flush: the
-//                     mask stays valid across it, and a later hit in the same word joins it.)  Before the atomic it loads the word
-//                     plainly and skips the atomic when every bit is there: bits are only ever set while marking, so a stale read can
-//                     only cause a redundant atomic.  Nothing is stored per base.
+//   k_color_mark<W>   the window walker (k_window.h) over k_quant's tiles (QUANT_TILE positions, QUANT_RUN per lane, extension) with the
+//                     marking sink: instead of one atomic per hit a lane keeps (word index, mask) in registers, ORs the hit's bit into
+//                     the mask and writes the mask with one atomic OR when the word index changes -- hits walk up on strand 0 and down
+//                     on strand 1 -- and at the end of its run.  (A miss does not flush: the mask stays valid across it, and a later
+//                     hit in the same word joins it.)  Before the atomic it loads the word plainly and skips the atomic when every bit
+//                     is there: bits are only ever set while marking, so a stale read can only cause a redundant atomic.  Nothing is
+//                     stored per base.
 //   k_color_ustart    one lane per unitig: the bit of its first position
 //   k_color_heads     one lane per 32-position word: the N plane words and each one's predecessor bit -> the word's head mask (stored: the
 //                     emit pass reads 4 bytes per word, not N), heads per wave (a tile is the 64 words of a wave: no LDS), positions with a
@@ -40,15 +40,8 @@ constexpr int COLOR_THREADS = 256;                  // (a multiple of 64: the ru
 constexpr int COLOR_AGG_ROUNDS = 4;                 // wave-aggregated adds before the per-lane fallback (k_color_number)
 constexpr uint64_t COLOR_EMPTY = 0xFFFFFFFFFFFFFFFFULL;
 
-struct ColorMarkParams {
-    const uint8_t* text; uint64_t n_text;   // one batch of the caller's bases
-    uint64_t n_out;                         // windows that START in [0, n_out) are this batch's
-    const uint32_t* bnd; uint32_t n_bnd;    // the sequence ends inside the batch, ascending; the last one is n_text
-    int k; int extend;
-    const uint8_t* packed; const uint64_t* unitig_off; const uint32_t* unitig_len; const uint64_t* kmer_off;
-    const uint64_t* slots; uint64_t mask;
+struct ColorMarkParams : WindowParams {     // out: [0] windows looked at  [1] windows found  [2] of those, answered by extension  [3] atomics issued
     uint32_t* plane; uint64_t n_words;      // the colour's plane: ceil(P / 32) words
-    uint64_t* out;                          // [0] windows looked at  [1] windows found  [2] of those, answered by extension  [3] atomics issued
 };
 
 // the lane's pending bits go to the plane: -> atomics issued (0 or 1)
@@ -59,86 +52,31 @@ CDBG_DEV uint32_t color_flush(const ColorMarkParams& P, uint64_t w, uint32_t m) 
     return 1u;
 }
 
+struct ColorMarkSink {
+    static constexpr bool PALINDROME_STRAND0 = false;
+    const ColorMarkParams& P;
+    uint64_t u_pos;                                         // the first position of the latest hit's unitig
+    uint64_t cur_w; uint32_t cur_m;                         // the bits not yet written: a word of the plane and a mask
+    uint64_t n_atom;
+    CDBG_DEV void fresh(uint64_t u) { u_pos = P.kmer_off[u]; }
+    CDBG_DEV void window(int, bool found, uint64_t, uint32_t o, uint32_t) {
+        if (!found) return;
+        const uint64_t at = u_pos + o, w = at >> 5;
+        if (w != cur_w) { n_atom += color_flush(P, cur_w, cur_m); cur_w = w; cur_m = 0; }
+        cur_m |= 1u << (uint32_t)(at & 31u);
+    }
+    CDBG_DEV void finish() { n_atom += color_flush(P, cur_w, cur_m); }
+};
+
 template <int W>
 __global__ void __launch_bounds__(QUANT_THREADS) k_color_mark(ColorMarkParams P) {
-    CDBG_SHARED uint8_t code[QUANT_TILE + QUERY_HALO];      // 0 .. 3, 0xFF: a byte outside ACGTacgt (or behind the batch)
-    const int tid = (int)threadIdx.x, k = P.k;
+    CDBG_SHARED uint8_t code[QUANT_TILE + QUERY_HALO];
     const uint64_t tile0 = (uint64_t)blockIdx.x * QUANT_TILE;
-    for (int i = tid; i < QUANT_TILE + k - 1; i += QUANT_THREADS) {
-        const uint64_t g = tile0 + (uint64_t)i;
-        const uint32_t c = g < P.n_text ? P.text[g] : (uint32_t)'\n';
-        code[i] = base_valid(c) ? (uint8_t)base_code(c) : (uint8_t)0xFF;
-    }
+    window_stage<QUANT_TILE, QUANT_THREADS>(P, tile0, code);
     __syncthreads();
-    const int p0 = tid * QUANT_RUN;
-    uint64_t n_win = 0, n_found = 0, n_ext = 0, n_atom = 0;
-    if (tile0 + (uint64_t)p0 < P.n_out) {
-        uint32_t lo = 0, hi = P.n_bnd - 1;                   // the first sequence end behind p0 (bnd[n_bnd - 1] = n_text is one)
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)P.bnd[mid] > tile0 + (uint64_t)p0) hi = mid; else lo = mid + 1; }
-        uint32_t bi = lo; uint64_t seq_end = P.bnd[bi];
-        int ok_from = p0;                                   // windows that start before it hold an invalid byte
-        Kmer<W> fw = Kmer<W>::zero();
-        for (int j = p0; j < p0 + k - 1; ++j) {
-            uint32_t c = code[j];
-            if (c == 0xFFu) { ok_from = j + 1; c = 0; }
-            fw.push_right(k, c);
-        }
-        Kmer<W> rc = fw.rc(k);
-        // the latest hit: arena offset of its unitig, the unitig's first position, its k-mer positions, the offset in it, the strand
-        bool have = false; uint64_t u_base = 0, u_pos = 0; uint32_t u_npos = 0, o = 0, strand = 0;
-        uint64_t cur_w = 0; uint32_t cur_m = 0;             // the bits not yet written: a word of the plane and a mask
-        for (int i = 0; i < QUANT_RUN; ++i) {
-            const int p = p0 + i, j = p + k - 1;
-            const uint64_t g = tile0 + (uint64_t)p;
-            uint32_t c = code[j];
-            if (c == 0xFFu) { ok_from = j + 1; c = 0; }
-            fw.push_right(k, c); rc.push_left(k, 3u - c);
-            bool valid = false;
-            if (g < P.n_out) {
-                while (g >= seq_end) seq_end = P.bnd[++bi];
-                valid = p >= ok_from && g + (uint64_t)k <= seq_end;
-            }
-            bool hit = false;
-            if (valid) {
-                ++n_win;
-                if (have) {                                 // (the window before this one was valid and hit: same sequence, no invalid byte between)
-                    if (strand == 0) { if (o + 1u < u_npos && packed_base(P.packed, u_base + o + (uint64_t)k) == c) { ++o; hit = true; } }
-                    else if (o >= 1u && packed_base(P.packed, u_base + o - 1u) == 3u - c) { --o; hit = true; }
-                    n_ext += hit ? 1u : 0u;
-                }
-                if (!hit) {
-                    uint64_t s = index_hash<W>(rc < fw ? rc : fw) & P.mask, probes = 0, at = INDEX_EMPTY;
-                    bool done, rev = false;
-#pragma clang loop unroll(disable)
-                    do {                                    // single exit; the table holds at least one empty slot
-                        const uint64_t v = P.slots[s];
-                        bool f = false, r = false;
-                        if (v != INDEX_EMPTY) {
-                            const Kmer<W> x = packed_kmer<W>(P.packed, P.unitig_off[v >> 32] + (v & 0xFFFFFFFFULL), k);
-                            f = x == fw; r = !f && x == rc;
-                        }
-                        at = (f | r) ? v : at; rev = r;
-                        done = (v == INDEX_EMPTY) | f | r;
-                        s = (s + 1) & P.mask; ++probes;
-                    } while (!done && probes <= P.mask);
-                    if (at != INDEX_EMPTY) {
-                        const uint64_t u = at >> 32;
-                        o = (uint32_t)at; strand = rev ? 1u : 0u; hit = true;
-                        u_base = P.unitig_off[u]; u_pos = P.kmer_off[u]; u_npos = P.unitig_len[u] - (uint32_t)k + 1u;
-                    }
-                }
-                if (hit) {
-                    ++n_found;
-                    const uint64_t at = u_pos + o, w = at >> 5;
-                    if (w != cur_w) { n_atom += color_flush(P, cur_w, cur_m); cur_w = w; cur_m = 0; }
-                    cur_m |= 1u << (uint32_t)(at & 31u);
-                }
-            }
-            have = hit && P.extend != 0;
-        }
-        n_atom += color_flush(P, cur_w, cur_m);
-    }
-    n_win = wave_sum_u64(n_win); n_found = wave_sum_u64(n_found); n_ext = wave_sum_u64(n_ext); n_atom = wave_sum_u64(n_atom);
+    ColorMarkSink sink{ P, 0, 0, 0, 0 };
+    const WindowTally t = window_walk<W, QUANT_RUN, true>(P, tile0, code, sink);
+    const uint64_t n_win = wave_sum_u64(t.windows), n_found = wave_sum_u64(t.found), n_ext = wave_sum_u64(t.extended), n_atom = wave_sum_u64(sink.n_atom);
     if ((threadIdx.x & 63) == 0 && n_win) {
         atomic_add_u64(&P.out[0], n_win);
         if (n_found) atomic_add_u64(&P.out[1], n_found);
@@ -208,8 +146,7 @@ __global__ void __launch_bounds__(COLOR_THREADS) k_color_runs(ColorRunParams P) 
     bool single = false;
     if (r < P.n_runs) {
         const uint64_t g = P.start[r], end = r + 1 < P.n_runs ? P.start[r + 1] : P.n_pos;
-        uint64_t lo = 0, hi = P.n_unitigs;                      // the unitig of position g: the last u with kmer_off[u] <= g
-        while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (P.kmer_off[mid] <= g) lo = mid; else hi = mid; }
+        const uint64_t lo = last_le(P.kmer_off, 0, P.n_unitigs, g);   // the unitig of position g
         const uint32_t o = (uint32_t)(g - P.kmer_off[lo]), n = (uint32_t)(end - g);
         P.offset[r] = o; P.len[r] = n;
         if (o == 0u) { P.run_off[lo] = r; single = n == P.unitig_len[lo] - (uint32_t)P.k + 1u; }

@@ -62,9 +62,7 @@ CDBG_DEV bool cq_run_interval(const ColorQueryParams& P, uint64_t r, uint64_t& u
 
 // the last colour run in [a, b) whose offset is <= o (a when there is none: the first run of a unitig starts at offset 0)
 CDBG_DEV uint64_t cq_run_of(const uint32_t* cl_offset, uint64_t a, uint64_t b, uint32_t o) {
-    uint64_t lo = a, hi = b;
-    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (cl_offset[mid] <= o) lo = mid; else hi = mid; }
-    return lo;
+    return last_le(cl_offset, a, b, o);
 }
 
 __global__ void __launch_bounds__(CQ_THREADS) k_cq_span(ColorQueryParams P) {
@@ -85,9 +83,7 @@ __global__ void __launch_bounds__(CQ_THREADS) k_cq_emit(ColorQueryParams P) {
     const uint64_t s = (uint64_t)blockIdx.x * CQ_THREADS + threadIdx.x;
     if (s <= P.n_seqs) { const uint64_t r = P.run_off[s]; P.seg_off[s] = P.seg_scan[r <= P.n_runs ? r : P.n_runs]; }
     if (s >= P.n_segs) return;
-    uint64_t lo_r = 0, hi_r = P.n_runs;                     // the thread run of segment s: the last r with seg_scan[r] <= s
-    while (hi_r - lo_r > 1) { const uint64_t mid = (lo_r + hi_r) >> 1; if (P.seg_scan[mid] <= s) lo_r = mid; else hi_r = mid; }
-    const uint64_t r = lo_r, j = s - P.seg_scan[r];
+    const uint64_t r = last_le(P.seg_scan, 0, P.n_runs, s), j = s - P.seg_scan[r];   // the thread run of segment s
     uint64_t u; uint32_t lo, hi, strand;
     uint64_t start = 0, place = INDEX_EMPTY; uint32_t len = 0, cls = 0;
     if (cq_run_interval(P, r, u, lo, hi, strand)) {

@@ -13,10 +13,10 @@
 //                      its k-mer: no pending state, no key to publish.  Which k-mer ends in which slot depends on the arrival order,
 //                      what a lookup returns does not: a built graph spells every k-mer once, a loaded set may repeat k-mers and the
 //                      slot then holds the SMALLEST (unitig, offset) of the occurrences.
-//   k_query<W>         one workgroup per tile of query text with a k - 1 halo, staged as 2-bit codes in LDS; a lane rolls both strands
-//                      over QUERY_RUN consecutive positions, keeps the last byte outside ACGTacgt and the end of its sequence, probes,
-//                      and compares every occupant with its forward k-mer (strand 0) and its reverse complement (strand 1) until a hit
-//                      or an empty slot.  The hit words go through LDS and leave as coalesced 8-byte stores, one per position.
+//   index_find<W>      the read-only probe of every consumer: hash the canonical one of a window's two k-mers, then compare every occupant
+//                      with the forward k-mer (strand 0) and its reverse complement (strand 1) until a hit or an empty slot.
+//   k_query<W>         the window walker (k_window.h) over tiles of QUERY_TILE positions, QUERY_RUN per lane, without extension, with
+//                      the hit-word sink: the words go through LDS and leave as coalesced 8-byte stores, one per position.
 // The arena is little-endian by base (base j = bits 2 (j & 3) of byte j >> 2), Kmer<W> keeps the first base in its highest bits:
 // packed_kmer() is the one place that turns one into the other, at any 2-bit alignment.
 #pragma once
@@ -72,6 +72,13 @@ CDBG_DEV uint64_t index_hash(const Kmer<W>& c) {
     return h;
 }
 
+// the last i in [lo, hi) with off[i] <= g (lo when there is none): the unitig of a k-mer position in kmer_off[], the run of a segment in a scan
+template <class T>
+CDBG_DEV uint64_t last_le(const T* off, uint64_t lo, uint64_t hi, T g) {
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (off[mid] <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+
 struct IndexParams {
     uint64_t n_unitigs; int k;
     const uint64_t* unitig_off; const uint32_t* unitig_len; const uint8_t* packed;
@@ -93,9 +100,7 @@ __global__ void k_index_insert(IndexParams P) {
     uint64_t n_ins = 0, n_new = 0, n_lost = 0;
     for (uint64_t first = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * INDEX_RUN; first < P.n_pos; first += stride) {
         const uint64_t end = first + INDEX_RUN < P.n_pos ? first + INDEX_RUN : P.n_pos;
-        uint64_t lo = 0, hi = P.n_unitigs;                      // the unitig of position `first`: the last u with kmer_off[u] <= first
-        while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (P.kmer_off[mid] <= first) lo = mid; else hi = mid; }
-        uint64_t u = lo, g = first;
+        uint64_t u = last_le(P.kmer_off, 0, P.n_unitigs, first), g = first;   // the unitig of position `first`
         while (g < end) {
             const uint64_t k0 = P.kmer_off[u], k1 = P.kmer_off[u + 1];
             if (g >= k1) { ++u; continue; }
@@ -131,82 +136,55 @@ __global__ void k_index_insert(IndexParams P) {
     if ((threadIdx.x & 63) == 0 && n_ins) { atomic_add_u64(&P.out[0], n_ins); atomic_add_u64(&P.out[1], n_new); if (n_lost) atomic_add_u64(&P.out[2], n_lost); }
 }
 
-struct QueryParams {
-    const uint8_t* text; uint64_t n_text;   // one batch of the caller's bases
-    uint64_t n_out;                         // positions of it to answer: hits[0 .. n_out)
-    const uint32_t* bnd; uint32_t n_bnd;    // the sequence ends inside the batch, ascending; the last one is n_text
-    int k;
-    const uint8_t* packed; const uint64_t* unitig_off; const uint64_t* slots; uint64_t mask;
-    uint64_t* hits;
-    uint64_t* out;                          // (CDBG_PROFILE_PHASES builds) [0] k-mers looked up  [1] slots read
+// where the table holds the window whose strands are fw and rc: the slot value (unitig << 32 | offset) or INDEX_EMPTY, the strand it
+// matched on (a k-mer that is its own reverse complement: strand 0), and the slots read.  Read-only; k_index_insert's CAS loop is its own.
+template <int W>
+CDBG_DEV uint64_t index_find(const Kmer<W>& fw, const Kmer<W>& rc, int k, const uint8_t* packed, const uint64_t* unitig_off,
+                             const uint64_t* slots, uint64_t mask, uint32_t& strand, uint64_t& probes) {
+    uint64_t s = index_hash<W>(rc < fw ? rc : fw) & mask, n = 0, at = INDEX_EMPTY;
+    bool done, rev = false;
+#pragma clang loop unroll(disable)
+    do {                                                    // single exit; the table holds at least one empty slot
+        const uint64_t v = slots[s];
+        bool f = false, r = false;
+        if (v != INDEX_EMPTY) {
+            const Kmer<W> x = packed_kmer<W>(packed, unitig_off[v >> 32] + (v & 0xFFFFFFFFULL), k);
+            f = x == fw; r = !f && x == rc;
+        }
+        at = (f | r) ? v : at; rev = r;
+        done = (v == INDEX_EMPTY) | f | r;
+        s = (s + 1) & mask; ++n;
+    } while (!done && n <= mask);
+    strand = rev ? 1u : 0u; probes = n;
+    return at;
+}
+
+}  // namespace cdbg
+
+#include "k_window.h"                                       // (needs everything above; k_query below needs it)
+
+namespace cdbg {
+
+struct QueryParams : WindowParams {         // out: (CDBG_PROFILE_PHASES builds) [0] k-mers looked up  [1] slots read
+    uint64_t* hits;                         // [n_out]
 };
 
 template <int W>
 __global__ void k_query(QueryParams P) {
-    CDBG_SHARED uint8_t code[QUERY_TILE + QUERY_HALO];      // 0 .. 3, 0xFF: a byte outside ACGTacgt (or behind the batch)
+    CDBG_SHARED uint8_t code[QUERY_TILE + QUERY_HALO];
     CDBG_SHARED uint64_t hit[QUERY_TILE];
-    const int tid = (int)threadIdx.x, k = P.k;
     const uint64_t tile0 = (uint64_t)blockIdx.x * QUERY_TILE;
-    for (int i = tid; i < QUERY_TILE + k - 1; i += QUERY_THREADS) {
-        const uint64_t g = tile0 + (uint64_t)i;
-        const uint32_t c = g < P.n_text ? P.text[g] : (uint32_t)'\n';
-        code[i] = base_valid(c) ? (uint8_t)base_code(c) : (uint8_t)0xFF;
-    }
+    window_stage<QUERY_TILE, QUERY_THREADS>(P, tile0, code);
     __syncthreads();
-    const int p0 = tid * QUERY_RUN;
-    uint64_t n_q = 0, n_probe = 0;
-    if (tile0 + (uint64_t)p0 < P.n_out) {
-        uint32_t lo = 0, hi = P.n_bnd - 1;                   // the first sequence end behind p0 (bnd[n_bnd - 1] = n_text is one)
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)P.bnd[mid] > tile0 + (uint64_t)p0) hi = mid; else lo = mid + 1; }
-        uint32_t bi = lo; uint64_t seq_end = P.bnd[bi];
-        int ok_from = p0;                                   // windows that start before it hold an invalid byte
-        Kmer<W> fw = Kmer<W>::zero();
-        for (int j = p0; j < p0 + k - 1; ++j) {
-            uint32_t c = code[j];
-            if (c == 0xFFu) { ok_from = j + 1; c = 0; }
-            fw.push_right(k, c);
-        }
-        Kmer<W> rc = fw.rc(k);                              // once per run (of 'A' + the first k - 1 bases: the roll below drops the A's complement)
-        for (int i = 0; i < QUERY_RUN; ++i) {
-            const int p = p0 + i, j = p + k - 1;
-            const uint64_t g = tile0 + (uint64_t)p;
-            uint32_t c = code[j];
-            if (c == 0xFFu) { ok_from = j + 1; c = 0; }
-            fw.push_right(k, c); rc.push_left(k, 3u - c);
-            uint64_t h = INDEX_EMPTY;
-            if (g < P.n_out) {
-                while (g >= seq_end) seq_end = P.bnd[++bi];
-                if (p >= ok_from && g + (uint64_t)k <= seq_end) {
-                    uint64_t s = index_hash<W>(rc < fw ? rc : fw) & P.mask, probes = 0;
-                    bool done;
-#pragma clang loop unroll(disable)
-                    do {                                    // single exit; the table holds at least one empty slot
-                        const uint64_t v = P.slots[s];
-                        bool f = false, r = false;
-                        if (v != INDEX_EMPTY) {
-                            const Kmer<W> x = packed_kmer<W>(P.packed, P.unitig_off[v >> 32] + (v & 0xFFFFFFFFULL), k);
-                            f = x == fw; r = !f && x == rc;   // (a k-mer that is its own reverse complement: strand 0)
-                        }
-                        h = (f | r) ? (((v >> 32) << 33) | ((v & 0xFFFFFFFFULL) << 1) | (r ? 1ULL : 0ULL)) : h;
-                        done = (v == INDEX_EMPTY) | f | r;
-                        s = (s + 1) & P.mask; ++probes;
-                    } while (!done && probes <= P.mask);
-                    ++n_q; n_probe += probes;
-                }
-            }
-            hit[p] = h;
-        }
-    }
+    HitWordSink<false> sink{ hit };
+    const WindowTally t = window_walk<W, QUERY_RUN, false>(P, tile0, code, sink);
     __syncthreads();
-    for (int i = tid; i < QUERY_TILE; i += QUERY_THREADS) {
-        const uint64_t g = tile0 + (uint64_t)i;
-        if (g < P.n_out) P.hits[g] = hit[i];
-    }
+    window_store_hits<QUERY_TILE, QUERY_THREADS>(hit, tile0, P.n_out, P.hits);
 #if defined(CDBG_PROFILE_PHASES) && !defined(CDBG_HOSTSIM)
-    n_q = wave_sum_u64(n_q); n_probe = wave_sum_u64(n_probe);
+    const uint64_t n_q = wave_sum_u64(t.windows), n_probe = wave_sum_u64(t.probes);
     if ((threadIdx.x & 63) == 0 && n_q) { atomic_add_u64(&P.out[0], n_q); atomic_add_u64(&P.out[1], n_probe); }
 #else
-    (void)n_q; (void)n_probe;
+    (void)t;
 #endif
 }
 
