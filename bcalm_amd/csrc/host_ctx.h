@@ -499,7 +499,7 @@ int read_u32(const uint32_t* dptr, uint32_t* out, size_t n = 1) {
 }
 int check_device_error(cdbg_ctx* c, const char* where) {
     uint32_t e = 0; CK(read_u32(c->derr.p, &e));
-    if (e) return fail(CDBG_E_INTERNAL, "%s: device reported error %u (1 solid overflow, 2 scratch sizing, 3 piece overflow, 4 unitig overflow, 5 glue log overflow, 9 junction-ownership flag of a k-mer wrong [simulator build only])", where, e);
+    if (e) return fail(CDBG_E_INTERNAL, "%s: device reported error %u (1 solid overflow, 2 scratch sizing, 3 piece overflow, 4 unitig overflow, 5 glue log overflow, 9 junction-ownership flag of a k-mer wrong [simulator build only], 10 k_walk_copy stored outside its lane's unitig [simulator build only])", where, e);
     HIPCK(hipGetLastError());
     return CDBG_OK;
 }

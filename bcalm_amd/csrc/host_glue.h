@@ -99,14 +99,17 @@ int glue_walk(cdbg_ctx* c, bool* done) {
     const uint64_t spans = (NS + WALK_SPAN - 1) / WALK_SPAN, wave_grid = (spans + WALK_THREADS / 64 - 1) / (WALK_THREADS / 64);
     WalkMeasureParams mp{ c->walk_rec.p, c->walk_heads.p, n_heads, c->walk_hlen.p, max_steps, c->rank_flag.p };
     CDBG_LAUNCH(k_walk_measure, wave_grid, WALK_THREADS, s, mp);
-    WalkPlaceParams pp{ n_heads, c->walk_hlen.p, c->walk_hoff.p, c->k, c->cursors.p + 2, c->cursors.p + 3, ucap, ocap, c->derr.p };
+    WalkPlaceParams pp{ n_heads, c->walk_hlen.p, c->walk_hoff.p, c->k, c->cursors.p + 2, c->cursors.p + 3, ucap, ocap, c->derr.p,
+                        c->unitig_off.p, c->unitig_len.p };
     CDBG_LAUNCH(k_walk_place, spans, WALK_THREADS, s, pp);
     WalkCopyParams wp{};
     wp.k = c->k; wp.rec = c->walk_rec.p; wp.piece_bases = c->piece_bases.p;
     wp.heads = c->walk_heads.p; wp.n_heads = n_heads; wp.hlen = c->walk_hlen.p; wp.hoff = c->walk_hoff.p;
-    wp.unitig_off = c->unitig_off.p; wp.unitig_len = c->unitig_len.p; wp.unitig_kc = c->unitig_kc.p; wp.out = c->unitig_bases.p; wp.visited = c->dstats.p + 5;
-    wp.piece_ab = c->prm.all_abundance_counts ? c->piece_ab.p : nullptr; wp.unitig_ab = c->unitig_ab.p;
-    CDBG_LAUNCH(k_walk_copy, wave_grid, WALK_THREADS, s, wp);
+    wp.unitig_len = c->unitig_len.p; wp.unitig_kc = c->unitig_kc.p; wp.out = c->unitig_bases.p; wp.visited = c->dstats.p + 5;
+    wp.piece_ab = c->prm.all_abundance_counts ? c->piece_ab.p : nullptr; wp.unitig_ab = c->unitig_ab.p; wp.error = c->derr.p;
+    // k >= 9: a lane collects its unitig's bytes and stores whole aligned 16-byte chunks; below, a piece can be shorter than one 8-byte load
+    if (c->k >= 9) CDBG_LAUNCH(k_walk_copy<true>, wave_grid, WALK_THREADS, s, wp);
+    else CDBG_LAUNCH(k_walk_copy<false>, wave_grid, WALK_THREADS, s, wp);
     HIPCK(hipStreamSynchronize(s));
     uint64_t d[2]; CK(read_u64(c->dstats.p + 4, d, 2));      // live, visited
     uint32_t gave_up = 0; CK(read_u32(c->rank_flag.p, &gave_up));

@@ -18,6 +18,13 @@
 // 18.5 ms of ranking + heads + emit -- a quarter of the lanes busy (the longest of 64 chains sets the pace) at 4 waves per
 // SIMD.  This version keeps every lane on a chain and needs no LDS: 3.2 + 0.6 + 6.8 ms.
 //
+// The copy then sat on the chip's rate of scattered store REQUESTS (187 M sectors written for an arena of 28 M: a piece that is
+// not the first of its chain brings 7.5 new bytes, which left as one or two unaligned stores of at most 8).  Now a lane keeps the
+// next 16 bytes of its unitig in registers and stores a chunk when it is full and aligned (WalkWin); only the two ragged ends
+// of a unitig leave as 8-byte stores, and k_walk_place writes unitig_off / unitig_len, where consecutive threads hold
+// consecutive unitigs.  k < 9 keeps the copy piece by piece.  Request model, ceiling, before / after:
+// profiles/r08_walk_copy_stores.log.
+//
 // What a walk cannot do -- chains longer than max_steps (error-free reads: one unitig of 10^5 pieces), closed chains
 // (no head: the visited-piece count falls short) -- is reported to the host, which runs the ranking path of k_glue.h on
 // the same link[]; the context then stays on that path.
@@ -138,7 +145,8 @@ __global__ void __launch_bounds__(WALK_THREADS) k_walk_measure(WalkMeasureParams
 
 // ---- (C) place: the kept heads of a span get consecutive unitig ids and consecutive room in the arena from ONE device
 // reservation per span; hlen becomes unitig id + 1 (0: not kept), hoff the unitig's offset ----
-struct WalkPlaceParams { const uint64_t* n_heads; uint32_t* hlen; uint64_t* hoff; int k; uint64_t* n_unitigs; uint64_t* out_cursor; uint64_t unitig_cap, out_cap; uint32_t* error; };
+struct WalkPlaceParams { const uint64_t* n_heads; uint32_t* hlen; uint64_t* hoff; int k; uint64_t* n_unitigs; uint64_t* out_cursor; uint64_t unitig_cap, out_cap; uint32_t* error;
+                         uint64_t* unitig_off; uint32_t* unitig_len; };
 __global__ void __launch_bounds__(WALK_THREADS) k_walk_place(WalkPlaceParams P) {
     CDBG_SHARED uint32_t s_wn[WALK_THREADS / 64]; CDBG_SHARED uint64_t s_wl[WALK_THREADS / 64];
     CDBG_SHARED uint64_t s_ubase, s_obase;
@@ -177,8 +185,10 @@ __global__ void __launch_bounds__(WALK_THREADS) k_walk_place(WalkPlaceParams P) 
 #pragma unroll
     for (int i = 0; i < WALK_SPT; ++i) {
         if (!kl[i]) continue;
+        const uint32_t len = kl[i] + (uint32_t)P.k - 1u;
         P.hlen[i0 + i] = fits ? (uint32_t)uid + 1u : 0u; P.hoff[i0 + i] = off;
-        ++uid; off += (uint64_t)kl[i] + (uint64_t)P.k - 1u;
+        if (fits) { P.unitig_off[uid] = off; P.unitig_len[uid] = len; }   // (consecutive ids in consecutive threads: the copy's lanes would scatter them)
+        ++uid; off += (uint64_t)len;
     }
 }
 
@@ -186,22 +196,107 @@ __global__ void __launch_bounds__(WALK_THREADS) k_walk_place(WalkPlaceParams P) 
 struct WalkCopyParams {
     int k; const uint4* rec; const uint8_t* piece_bases;
     const uint32_t* heads; const uint64_t* n_heads; const uint32_t* hlen; const uint64_t* hoff;
-    uint64_t* unitig_off; uint32_t* unitig_len; uint64_t* unitig_kc; uint8_t* out; uint64_t* visited;
+    const uint32_t* unitig_len; uint64_t* unitig_kc; uint8_t* out; uint64_t* visited;   // (unitig_len: written by k_walk_place; read by the simulator's guard only)
     const uint32_t* piece_ab; uint32_t* unitig_ab;          // optional per-k-mer abundances, indexed like the bases
+    uint32_t* error;
 };
+
+// A lane's window on the arena (CHUNKED copy): its unitig's next bytes, collected at their place inside the 16-byte-aligned
+// chunk they belong to, and stored with ONE request when the chunk is full.  The scattered-store rate is per request, not per
+// byte (profiles/r04_micro_sector_store.log): a piece adds 7.5 bytes on average, which left as 1.6 requests of at most 8 bytes.
+//   st 0: no chunk has left yet (bytes below the unitig's offset in the first chunk are not this lane's: they are never stored)
+//   st 1: the first chunk held fewer than 8 bytes of the unitig; they wait in `prev` for the chunk behind them, and leave with
+//         its first bytes as one 8-byte store that overlaps it
+//   st 2: `prev` = upper half of the chunk stored last (a tail shorter than 8 bytes leaves with the bytes in front of it)
+// Bytes of lo:hi at and above the fill count (pos & 15) are zero.
+struct WalkWin { uint64_t lo, hi, prev; uint32_t st; };
+// where a store of the lane may land: the arena, the lane's unitig [u0, u0 + ulen)
+struct WalkDst { uint8_t* out; uint64_t u0; uint32_t ulen; uint32_t* error; uint32_t flushes; };
+
+CDBG_DEV void wc_guard(WalkDst& D, uint64_t at, uint32_t bytes) {
+#ifdef CDBG_HOSTSIM
+    if (at < D.u0 || at + bytes > D.u0 + D.ulen) *D.error = 10;   // (the simulator build checks every arena store against the lane's unitig)
+#endif
+}
+CDBG_DEV void wc_st16(WalkDst& D, uint64_t at, uint64_t lo, uint64_t hi) {   // at: a multiple of 16 (the arena is allocated at one)
+    wc_guard(D, at, 16);
+#ifdef CDBG_HOSTSIM
+    if (at & 15u) *D.error = 10;
+    __builtin_memcpy(D.out + at, &lo, 8); __builtin_memcpy(D.out + at + 8, &hi, 8);
+#else
+    uint4 v; v.x = (uint32_t)lo; v.y = (uint32_t)(lo >> 32); v.z = (uint32_t)hi; v.w = (uint32_t)(hi >> 32);
+    *reinterpret_cast<uint4*>(D.out + at) = v;
+#endif
+}
+CDBG_DEV void wc_st8(WalkDst& D, uint64_t at, uint64_t w) { wc_guard(D, at, 8); st_unaligned_u64(D.out + at, w); }
+// bytes [r, r + 8) of the 16 bytes a:b, 0 <= r <= 8
+CDBG_DEV uint64_t wc_bytes8(uint64_t a, uint64_t b, uint32_t r) { return r == 0u ? a : r == 8u ? b : (a >> (8u * r)) | (b << (64u - 8u * r)); }
+// n bytes (9 .. 22: a whole unitig of k >= 9 bases that is too short for a chunk and its ends) of w0:w1:w2 to `at`
+CDBG_DEV void wc_store_small(WalkDst& D, uint64_t at, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t n) {
+    wc_st8(D, at, w0);
+    if (n >= 16u) { wc_st8(D, at + 8u, w1); if (n > 16u) wc_st8(D, at + n - 8u, wc_bytes8(w1, w2, n - 16u)); }
+    else wc_st8(D, at + n - 8u, wc_bytes8(w0, w1, n - 8u));
+}
+// the chunk at cb is full
+CDBG_DEV void wc_flush(WalkWin& B, WalkDst& D, uint64_t cb) {
+    ++D.flushes;
+    if (cb >= D.u0) {
+        wc_st16(D, cb, B.lo, B.hi);
+        if (B.st == 1u) { const uint32_t h = 16u - ((uint32_t)D.u0 & 15u); wc_st8(D, D.u0, B.prev | (B.lo << (8u * h))); }   // (h = 1 .. 7)
+        B.prev = B.hi; B.st = 2u;
+    } else {                                               // the unitig's first chunk: bytes [a, 16) are its own
+        const uint32_t a = (uint32_t)(D.u0 - cb);
+        if (a <= 8u) { wc_st8(D, D.u0, wc_bytes8(B.lo, B.hi, a)); if (a < 8u) wc_st8(D, cb + 8u, B.hi); B.prev = B.hi; B.st = 2u; }
+        else { B.prev = B.hi >> (8u * (a - 8u)); B.st = 1u; }
+    }
+}
+// c bytes (1 .. 8; the bytes of w above them are zero) to the arena position pos
+CDBG_DEV void wc_append(WalkWin& B, WalkDst& D, uint64_t pos, uint64_t w, uint32_t c) {
+    const uint32_t s = (uint32_t)pos & 15u;
+    if (s < 8u) { B.lo |= w << (8u * s); if (s) B.hi |= w >> (64u - 8u * s); }
+    else {
+        const uint32_t s8 = s - 8u;
+        B.hi |= w << (8u * s8);
+        if (s + c >= 16u) { wc_flush(B, D, pos - s); B.lo = s8 ? w >> (64u - 8u * s8) : 0ull; B.hi = 0; }
+    }
+}
+// the unitig ends at `end`: what the window still holds
+CDBG_DEV void wc_finish(WalkWin& B, WalkDst& D, uint64_t end) {
+    const uint32_t t = (uint32_t)end & 15u;
+    if (B.st == 2u) {
+        if (t >= 8u) { wc_st8(D, end - t, B.lo); if (t > 8u) wc_st8(D, end - 8u, wc_bytes8(B.lo, B.hi, t - 8u)); }
+        else if (t) wc_st8(D, end - 8u, wc_bytes8(B.prev, B.lo, t));   // (a chunk or 8 bytes of the first one left before: the 8 bytes are the unitig's own)
+    } else if (B.st == 1u) {                               // fewer than 8 bytes in the first chunk, the second one not full
+        const uint32_t h = 16u - ((uint32_t)D.u0 & 15u);
+        wc_store_small(D, D.u0, B.prev | (B.lo << (8u * h)), (B.lo >> (64u - 8u * h)) | (B.hi << (8u * h)), B.hi >> (64u - 8u * h), h + t);
+    } else {                                               // all of it inside one chunk: 9 .. 15 bytes from a < 8
+        const uint32_t a = (uint32_t)D.u0 & 15u;
+        wc_store_small(D, D.u0, wc_bytes8(B.lo, B.hi, a), B.hi >> (8u * a), 0, (uint32_t)(end - D.u0));
+    }
+}
+
+// CHUNKED: k >= 9 (a piece has at least 8 bases: every load is one of 8 bytes inside the piece); else the copy piece by piece
+template <bool CHUNKED>
 __global__ void __launch_bounds__(WALK_THREADS) k_walk_copy(WalkCopyParams P) {
     const int lane = threadIdx.x & 63;
     const uint64_t n_heads = *P.n_heads;
     const uint64_t wv = ((uint64_t)blockIdx.x * WALK_THREADS + threadIdx.x) >> 6;
     uint64_t next = wv * WALK_SPAN; const uint64_t end = next + WALK_SPAN < n_heads ? next + WALK_SPAN : n_heads;
     bool active = false; uint32_t e = 0, koff = 0, uid = 0, seen = 0; uint64_t kc = 0, uoff = 0;
+    WalkWin B{ 0, 0, 0, 0 }; WalkDst D{ P.out, 0, 0, P.error, 0 };
     for (;;) {
         const uint64_t need = __ballot(!active);
         if (next < end) {                                  // (uniform)
             const uint64_t my = next + walk_lane_rank(need, lane);
             if (!active && my < end) {
                 const uint32_t u1 = P.hlen[my];
-                if (u1) { uid = u1 - 1u; uoff = P.hoff[my]; e = P.heads[my]; koff = 0; kc = 0; active = true; }
+                if (u1) {
+                    uid = u1 - 1u; uoff = P.hoff[my]; e = P.heads[my]; koff = 0; kc = 0; active = true;
+                    B.lo = 0; B.hi = 0; B.st = 0; D.u0 = uoff;
+#ifdef CDBG_HOSTSIM
+                    D.ulen = P.unitig_len[uid];
+#endif
+                }
             }
             next += (uint64_t)__popcll(need);
         }
@@ -213,7 +308,32 @@ __global__ void __launch_bounds__(WALK_THREADS) k_walk_copy(WalkCopyParams P) {
             const uint64_t boff = (uint64_t)b.y | ((uint64_t)b.z << 32);
             kc += (uint64_t)a.w | ((uint64_t)b.x << 32);
             const bool fwd = (e & 1u) == END_LEFT;
-            walk_copy(P.piece_bases + boff, P.out + uoff + koff, nb, koff ? (uint32_t)P.k - 1u : 0u, fwd);   // (the overlap was written by the previous piece)
+            const uint32_t skip = koff ? (uint32_t)P.k - 1u : 0u;   // (the overlap came with the previous piece)
+            if constexpr (CHUNKED) {
+                const uint8_t* const src = P.piece_bases + boff;
+                uint64_t pos = uoff + koff + skip;
+                D.flushes = 0;
+                for (uint32_t i = skip; i < nb;) {             // 8 bases per load, the last 8 overlapping (walk_copy's loads)
+                    const uint32_t c = nb - i < 8u ? nb - i : 8u, j = i + c - 8u;
+                    const uint64_t w = fwd ? ld_unaligned_u64(src + j) : comp_ascii8_rev(ld_unaligned_u64(src + (nb - 8u - j)));
+                    wc_append(B, D, pos, w >> (8u * (8u - c)), c);
+                    pos += c; i += c;
+                }
+#ifdef CDBG_HOSTSIM
+                // (the simulator build, for the tests of the chunked copy: CDBG_SIM_WALK_TRACE=<file> gets one line per copied piece -- unitig,
+                //  its offset, the piece's first new byte in it, new bytes, forward?, chunks that left inside the piece, last piece of the unitig?)
+                if (const char* tf = getenv("CDBG_SIM_WALK_TRACE")) if (FILE* fp = fopen(tf, "a")) {
+                    fprintf(fp, "%u %llu %u %u %d %u %d\n", uid, (unsigned long long)uoff, koff + skip, nb - skip, fwd ? 1 : 0, D.flushes,
+                            ((e & 1u) ? a.y : a.x) == NONE32 ? 1 : 0);
+                    fclose(fp);
+                }
+#endif
+            } else {
+#ifdef CDBG_HOSTSIM
+                wc_guard(D, uoff + koff + skip, nb - skip);
+#endif
+                walk_copy(P.piece_bases + boff, P.out + uoff + koff, nb, skip, fwd);
+            }
             if (P.piece_ab) {                              // -all-abundance-counts: k-mer t of the piece -> k-mer koff + t (or mirrored)
                 const uint32_t* sa = P.piece_ab + boff + (P.k - 1);
                 uint32_t* da = P.unitig_ab + uoff + koff + (P.k - 1);
@@ -222,7 +342,10 @@ __global__ void __launch_bounds__(WALK_THREADS) k_walk_copy(WalkCopyParams P) {
             }
             koff += n; ++seen;
             const uint32_t nx = (e & 1u) ? a.y : a.x;
-            if (nx == NONE32) { P.unitig_off[uid] = uoff; P.unitig_len[uid] = koff + (uint32_t)P.k - 1u; P.unitig_kc[uid] = kc; active = false; }
+            if (nx == NONE32) {
+                if constexpr (CHUNKED) wc_finish(B, D, uoff + koff + (uint32_t)P.k - 1u);
+                P.unitig_kc[uid] = kc; active = false;          // (offset and length left in k_walk_place, coalesced)
+            }
             else e = nx;
         }
     }
